@@ -20,9 +20,14 @@ N > 1 runs two ways, with the same kernels and the same exchange:
   torchrun --nproc-per-node N bench.py --gpus N
                                one process per GPU, torch.distributed over RCCL.
 
-Three more legs time the real-mesh path (scenes too large for the LDS scene copy,
-traversed from HBM/L2), each under "legs" with its own roofline and ray mix; `value`
-is the main leg:
+A plain run does only what the headline needs: set-up, the counting launch, warmup, the timed steps,
+then the line.  --dump-outputs DIR also writes what the last timed step computed (the radiance
+accumulation and the sRGB8 frame, as rank 0 reads them) to DIR/accum.npy and DIR/out.npy in float32;
+the inputs are fixed by the arguments, so two builds can be compared array for array.
+
+--full adds the rest: the CPU baseline (N = 1) and three more legs that time the real-mesh path
+(scenes too large for the LDS scene copy, traversed from HBM/L2), each under "legs" with its own
+roofline and ray mix; `value` is the main leg:
   global_scene        a synthetic 1 M-triangle soup (SURVEY.md 8d generator), 1920x1080 @16 spp;
   surface_mesh        a closed 262k-triangle surface (torus-knot tube wound outward, as an
                       exported mesh is, so paths bounce off it), 1920x1080 @64 spp;
@@ -31,7 +36,7 @@ is the main leg:
                       OBJ would run in this mode (no real mesh fits the LDS copy), so the line
                       repeats this leg at top level as `c3_regime`, beside the Rubik `value`.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
        (tests: under torchrun, --backend gloo --same-device runs N ranks on one GPU, staging through the host)
 """
@@ -134,7 +139,14 @@ def parse(argv=None):
     ap.add_argument("--group", action="store_true",
                     help="run the in-process device group even at --gpus 1 (one RCCL rank: the N > 1 path's code)")
     ap.add_argument("--dump", default=None, help="rank 0 saves the assembled frame (npz) after the last step")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's arrays to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the real-mesh legs (each still subject to its --no-* option)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(st: dict) -> int:
@@ -614,6 +626,26 @@ def ray_kinds(st: dict) -> dict:
     return {"camera": cam, "shadow": sh, "bounce": b, "bounce_share": round(b / max(int(st["rays"]), 1), 4)}
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # the dump may take 64 MB in all; the rest is room for the file headers
+
+
+def dump_outputs(dirname, arrays: dict) -> None:
+    """The arrays as DIR/<name>.npy in float32.  When they exceed the budget together, every array above its equal
+    share is cut to a fixed, seeded sample of its pixels (rows of the last axis), in raster order: the same
+    pixels in every run and every build, so the files of two runs compare element for element."""
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            px = a.reshape(-1, a.shape[-1])
+            keep = share // (4 * px.shape[1])
+            a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))]
+        np.save(d / f"{name}.npy", a)
+
+
 def run_compute(run):
     return run.grp.parts[0].compute if isinstance(run, GroupRun) else run.c
 
@@ -669,6 +701,10 @@ def main(argv=None):
         fr = run.frame()
         if rank == 0:
             np.savez(args.dump, accum=fr[0], out=fr[1])
+    if args.dump_outputs:
+        fr = run.frame()  # (collective for N > 1: every rank calls it)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"accum": fr[0], "out": fr[1]})
     kname = timed_kernel(run_compute(run), args.scene)
     par = parallelism(args, mode, world, run)
     table = rank_table(per_ctx, run.rank_stats() if mode == "group" else [st], args, mode, world, dev)
@@ -680,7 +716,7 @@ def main(argv=None):
             ("global_scene", not args.no_global_leg, "synthetic", 1920, 1080, args.global_spp, args.global_tris),
             ("surface_mesh", not args.no_surface_leg, "torusknot", 1920, 1080, args.surface_spp, 0),
             ("airplane_materials", not args.no_airplane_leg, "airplane_knot", 1920, 1080, args.airplane_spp, 0)):
-        if not enabled:
+        if not (args.full and enabled):
             continue
         lsetup, lname = build_setup(scene, lw, lh, lspp, 5, ntri)
         l_el, l_rays, l_st, l_ctx, l_run = run_leg(lsetup, lspp, args, mode=mode, rank=rank, world=world,
@@ -761,7 +797,7 @@ def main(argv=None):
             line["group"] = {"mode": "torch.distributed, one process per GPU", "backend": args.backend,
                              "world_size": world,
                              "gather_bytes_per_frame": world * PAR_rows_pad(H, args.band_rows, world) * W * 4}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(setup, 2, args.cpu_seconds)
         else:
             line["cpu_baseline"] = None

@@ -93,6 +93,29 @@ def test_valu_issue_against_the_calibrated_rate(stub):
     assert g["valu_issue_calibrated"]["waves_per_simd"] == 5 and "8 waves" in g["valu_issue_calibrated"]["basis"]
 
 
+def test_dump_outputs_is_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole; past the budget, each array above its share is cut to the same seeded
+    pixels in every run (raster order), and the files stay within the budget."""
+    import numpy as np
+
+    acc = np.arange(50 * 40 * 4, dtype=np.float32).reshape(50, 40, 4)
+    img = (np.arange(50 * 40 * 4) % 251).astype(np.uint8).reshape(50, 40, 4)
+    bench.dump_outputs(tmp_path / "a", {"accum": acc, "out": img})
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "accum.npy"), acc)
+    # a budget that holds 3/4 of the two arrays: each is cut to 750 of its 2000 pixels
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 750 * 16)
+    bench.dump_outputs(tmp_path / "b", {"accum": acc, "out": img})
+    bench.dump_outputs(tmp_path / "c", {"accum": acc + 0.0, "out": img})
+    b, c = np.load(tmp_path / "b" / "accum.npy"), np.load(tmp_path / "c" / "accum.npy")
+    assert b.shape == (750, 4) and np.array_equal(b, c)
+    first = b[:, 0].astype(np.int64) // 4  # the pixel index each kept row came from
+    assert (np.diff(first) > 0).all() and np.array_equal(b, acc.reshape(-1, 4)[first])
+    assert np.array_equal(np.load(tmp_path / "b" / "out.npy"), img.reshape(-1, 4)[first].astype(np.float32))
+    assert b.nbytes + np.load(tmp_path / "b" / "out.npy").nbytes <= 2 * 750 * 16
+
+
 def test_code_hash_ignores_prose_but_not_code(tmp_path):
     """the code hash is the preprocessed translation unit of pathtrace.hip (comments and
     blank lines gone) plus the hipcc flags, so a comment edit in include/srt_amd.h or a kernel header leaves it

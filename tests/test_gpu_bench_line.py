@@ -16,9 +16,35 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line holds the headline alone (no legs, no C3 regime, no CPU baseline), and
+    --dump-outputs writes the last timed step's frame as float32 .npy files: the same arrays --dump saves."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--width", "96", "--height", "61", "--spp", "3", "--dump", str(tmp_path / "f.npz"),
+           "--dump-outputs", str(out)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=180, env=env)
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["legs"] == [] and line["c3_regime"] is None and line["cpu_baseline"] is None
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "fp32"
+    assert sorted(p.name for p in out.iterdir()) == ["accum.npy", "out.npy"]
+    acc, img = np.load(out / "accum.npy"), np.load(out / "out.npy")
+    assert acc.dtype == np.float32 and img.dtype == np.float32
+    assert acc.shape == (61, 96, 4) and img.shape == (61, 96, 4)
+    with np.load(tmp_path / "f.npz") as z:
+        assert np.array_equal(acc.view(np.uint32), z["accum"].view(np.uint32))
+        assert np.array_equal(img, z["out"].astype(np.float32))
+    assert acc[..., :3].max() > 0 and img.max() > 0
+
+
 def test_bench_line_carries_c3_regime_and_ray_kinds():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
            "--width", "320", "--height", "180", "--spp", "4", "--no-global-leg", "--surface-spp", "2",
            "--airplane-spp", "2"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)

@@ -6,7 +6,7 @@ run took the IL-pattern instance, as trees past 600 MB do; --sum: sum every non-
 (or sphere_kernel) dispatch of a single-workload run, whatever its instance, e.g. tools/pmc_configs.sh's
 C2 and C4)
 
-Each pass ran `python bench.py --steps 1 --warmup 0 --no-cpu-baseline`, so every leg's timed step
+Each pass ran `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`, so every leg's timed step
 launched its sample_kernel<false, ...> instance exactly once (the counting run is the <true, ...>
 instance).  Per leg and launch:
   SQ_INSTS_VALU, SQ_THREAD_CYCLES_VALU, SQ_LDS_IDX_ACTIVE, SQ_LDS_BANK_CONFLICT, SQ_WAVE_CYCLES,
@@ -100,7 +100,7 @@ for wl in sq:
         tcc = per_launch("pmc_tcc").get(wl, {})
         d.update({k: v for k, v in tcc.items()})
     d["source"] = (f"rocprofv3 --pmc passes ({tag}): SQ counters + GRBM_GUI_ACTIVE, FETCH_SIZE, WRITE_SIZE; "
-                   f"python bench.py --steps 1 --warmup 0 --no-cpu-baseline; per launch of the timed step")
+                   f"python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline; per launch of the timed step")
     d["code_hash"] = code
     data[wl] = d
     lane = d["SQ_THREAD_CYCLES_VALU"] / (64 * d["SQ_INSTS_VALU"])
