@@ -1,0 +1,273 @@
+// query.hip -- the ray-query service of include/srt_query.h: a device copy of the scene in
+// query_host.hpp's layout, and the launches of query_kernel (query.hpp).  A translation unit of its own:
+// pathtrace.hip and its headers (the device code srt_code_hash identifies) are only read.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/srt_query.h"
+#include "query.hpp"
+#include "query_host.hpp"
+
+#define QHIP_OK(expr)                                                         \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                   \
+      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
+      return SRT_ERR_HIP;                                                     \
+    }                                                                         \
+  } while (0)
+
+struct srt_query {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  float4* d_pairs = nullptr;
+  float4* d_roots = nullptr;
+  float4* d_tris = nullptr;
+  float* d_frames = nullptr;
+  uint32_t* d_ctr = nullptr;
+  uint32_t* d_stack = nullptr;  // HBM stacks of `stack_blocks` blocks (deep trees only)
+  int stack_blocks = 0;
+  size_t scene_bytes = 0;
+  uint32_t n_bvhs = 0, bvh_count = 0;
+  srt::query::StackPlan plan;
+  int max_blocks[2] = {0, 0};  // persistent grid of the closest / any instance
+  int refill_min = 0, claim_env = 0;
+  int last_blocks = 0;
+};
+
+namespace {
+
+using srt::query::kBlock;
+using srt::query::QParams;
+
+// gfx950 hands a block its LDS in units of 1/128 of the CU's 160 KiB; n blocks run together only when
+// each asks at most floor(128 / n) units ("occupancy").
+int LdsBlocksPerCu(size_t lds) {
+  const size_t gran = 160 * 1024 / 128;
+  return lds == 0 ? 1 << 30 : (int)(128 / ((lds + gran - 1) / gran));
+}
+
+template <bool ANY>
+const void* Instance(bool hbm, bool pack) {
+  if (hbm) return pack ? (const void*)srt::query::query_kernel<ANY, true, true>
+                       : (const void*)srt::query::query_kernel<ANY, true, false>;
+  return pack ? (const void*)srt::query::query_kernel<ANY, false, true>
+              : (const void*)srt::query::query_kernel<ANY, false, false>;
+}
+
+void FreeAll(srt_query* q) {
+  if (q->d_pairs) (void)hipFree(q->d_pairs);
+  if (q->d_roots) (void)hipFree(q->d_roots);
+  if (q->d_tris) (void)hipFree(q->d_tris);
+  if (q->d_frames) (void)hipFree(q->d_frames);
+  if (q->d_ctr) (void)hipFree(q->d_ctr);
+  if (q->d_stack) (void)hipFree(q->d_stack);
+  if (q->own_stream && q->stream) (void)hipStreamDestroy(q->stream);
+}
+
+int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bvhs) {
+  QHIP_OK(hipSetDevice(q->device));
+  if (!q->stream) {
+    QHIP_OK(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
+    q->own_stream = true;
+  }
+  std::vector<float> frames(16 * ((size_t)q->n_bvhs + 1), 0.0f);
+  for (uint32_t b = 0; b < q->n_bvhs; ++b) std::memcpy(&frames[16 * (size_t)b], bvhs[b].frame, 16 * sizeof(float));
+  const size_t pb = lay.pairs.size() * sizeof(float4), rb = lay.roots.size() * sizeof(float4),
+               tb = lay.tris.size() * sizeof(float4), fb = frames.size() * sizeof(float);
+  QHIP_OK(hipMalloc(&q->d_pairs, pb));
+  QHIP_OK(hipMalloc(&q->d_roots, rb));
+  QHIP_OK(hipMalloc(&q->d_tris, tb));
+  QHIP_OK(hipMalloc(&q->d_frames, fb));
+  QHIP_OK(hipMalloc(&q->d_ctr, 256));
+  QHIP_OK(hipMemcpyAsync(q->d_pairs, lay.pairs.data(), pb, hipMemcpyHostToDevice, q->stream));
+  QHIP_OK(hipMemcpyAsync(q->d_roots, lay.roots.data(), rb, hipMemcpyHostToDevice, q->stream));
+  QHIP_OK(hipMemcpyAsync(q->d_tris, lay.tris.data(), tb, hipMemcpyHostToDevice, q->stream));
+  QHIP_OK(hipMemcpyAsync(q->d_frames, frames.data(), fb, hipMemcpyHostToDevice, q->stream));
+  QHIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
+  q->scene_bytes = pb + rb + tb + fb;
+  // persistent grid: the blocks the device holds at once
+  hipDeviceProp_t prop;
+  QHIP_OK(hipGetDeviceProperties(&prop, q->device));
+  for (int any = 0; any < 2; ++any) {
+    const void* fn = any ? Instance<true>(q->plan.in_hbm, q->plan.packed) : Instance<false>(q->plan.in_hbm, q->plan.packed);
+    if (q->plan.lds_bytes > 48 * 1024)
+      QHIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
+    int per_cu = 0;
+    QHIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
+    per_cu = std::max(1, std::min(per_cu, LdsBlocksPerCu(q->plan.lds_bytes)));
+    if (q->plan.in_hbm) per_cu = std::min(per_cu, 4);  // each block holds an HBM stack area
+    q->max_blocks[any] = per_cu * std::max(1, prop.multiProcessorCount);
+  }
+  return SRT_OK;
+}
+
+template <bool ANY>
+int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
+  if (!q || (n && (!rays || !out))) return SRT_ERR_INVALID;
+  if (n == 0) return SRT_OK;
+  if (((uintptr_t)rays & 15u) || (!ANY && ((uintptr_t)out & 15u))) {
+    srt::SetError("srt_query: rays and hits must be 16-byte aligned");
+    return SRT_ERR_INVALID;
+  }
+  if (n > 0xFFF00000u) {
+    srt::SetError("srt_query: more than 2^32 - 2^20 rays in one call");
+    return SRT_ERR_LIMIT;
+  }
+  QHIP_OK(hipSetDevice(q->device));
+  const int blocks = (int)std::min<uint64_t>((uint64_t)q->max_blocks[ANY ? 1 : 0], ((uint64_t)n + kBlock - 1) / kBlock);
+  if (q->plan.in_hbm && blocks > q->stack_blocks) {  // grown when n grows (hipFree waits for the device)
+    if (q->d_stack) (void)hipFree(q->d_stack);
+    q->d_stack = nullptr;
+    q->stack_blocks = 0;
+    QHIP_OK(hipMalloc(&q->d_stack, q->plan.hbm_block_bytes * (size_t)blocks));
+    q->stack_blocks = blocks;
+  }
+  QParams qp;
+  std::memset(&qp, 0, sizeof qp);
+  qp.pairs = q->d_pairs;
+  qp.roots = q->d_roots;
+  qp.tris = q->d_tris;
+  qp.frames = q->d_frames;
+  qp.rays = reinterpret_cast<const float4*>(rays);
+  qp.out = out;
+  qp.ctr = q->d_ctr;
+  qp.gstack = q->d_stack;
+  qp.n = n;
+  qp.n_bvhs = q->n_bvhs;
+  qp.bvh_count = q->bvh_count;
+  // rays per claim: 64, or more (up to 256) while every wave of the grid still claims 8 times or more
+  const uint64_t waves = (uint64_t)blocks * (kBlock / 64);
+  const uint64_t per = (uint64_t)n / (waves * 64 * 8);
+  qp.claim = 64u * (uint32_t)(q->claim_env > 0 ? q->claim_env : std::max<uint64_t>(1, std::min<uint64_t>(4, per)));
+  qp.stack_entries = q->plan.entries;
+  qp.refill_min = q->refill_min;
+  QHIP_OK(hipMemsetAsync(q->d_ctr, 0, sizeof(uint32_t), q->stream));
+  void* args[] = {&qp};
+  QHIP_OK(hipLaunchKernel(Instance<ANY>(q->plan.in_hbm, q->plan.packed), dim3((unsigned)blocks), dim3(kBlock), args,
+                          q->plan.lds_bytes, q->stream));
+  q->last_blocks = blocks;
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_query_abi_version(void) { return SRT_QUERY_ABI_VERSION; }
+
+int srt_query_create(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes,
+                     uint32_t n_nodes, const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts,
+                     uint32_t n_verts, srt_query** out) {
+  if (!out) return SRT_ERR_INVALID;
+  *out = nullptr;
+  // host-side validation and re-layout first: a bad scene never reaches the device
+  srt::query::Layout lay;
+  std::string err;
+  if (int rc = srt::query::BuildLayout(bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, &lay, &err)) {
+    srt::SetError(err);
+    return rc;
+  }
+  if (lay.depth >= (1 << 20)) {
+    srt::SetError("BVH deeper than the query traversal stack supports (2^20 levels)");
+    return SRT_ERR_LIMIT;
+  }
+  srt_query* q = new srt_query();
+  q->device = device;
+  q->stream = static_cast<hipStream_t>(stream);
+  q->n_bvhs = q->bvh_count = n_bvhs;
+  q->plan = srt::query::PlanStack(lay, n_tris);
+  // Refill threshold ("Ray queries"): a scene the caches hold (Rubik, 74 KB) gains from
+  // refilling early (surface rays 1.90 ms with 1, 1.54 with 40-56, 1.59 with 64); the 262k-triangle knot
+  // (20 MB) loses (6.82 ms with 1, 7.5-7.9 with 16-64: fresh rays at the root beside deep ones touch more
+  // lines per load), so its waves take new rays only when every lane is done.  SRT_QUERY_REFILL=1..64 forces it.
+  const size_t scene_bytes = (lay.pairs.size() + lay.roots.size() + lay.tris.size()) * sizeof(float4);
+  const char* e = std::getenv("SRT_QUERY_REFILL");
+  q->refill_min = std::max(1, std::min(64, e ? std::atoi(e) : (scene_bytes < (1u << 20) ? 48 : 1)));
+  e = std::getenv("SRT_QUERY_CLAIM");
+  q->claim_env = e ? std::max(0, std::min(64, std::atoi(e))) : 0;
+  if (int rc = Upload(q, lay, bvhs)) {
+    FreeAll(q);
+    delete q;
+    return rc;
+  }
+  *out = q;
+  return SRT_OK;
+}
+
+int srt_query_create_obj(int device, void* stream, const srt_scene* s, srt_query** out) {
+  if (!s || !out) return SRT_ERR_INVALID;
+  uint32_t sz[5] = {0, 0, 0, 0, 0};
+  if (int rc = srt_scene_sizes(s, sz)) return rc;
+  std::vector<srt_bvh_record> bvhs(sz[0]);
+  std::vector<srt_bvh_node> nodes(sz[1]);
+  std::vector<srt_material_obj> mats(sz[2]);
+  std::vector<float> alb(3 * (size_t)sz[2]);
+  std::vector<srt_triangle> tris(sz[3]);
+  std::vector<srt_vertex> verts(sz[4]);
+  if (int rc = srt_scene_copy(s, bvhs.data(), nodes.data(), mats.data(), alb.data(), tris.data(), verts.data()))
+    return rc;
+  return srt_query_create(device, stream, bvhs.data(), sz[0], nodes.data(), sz[1], tris.data(), sz[3], verts.data(),
+                          sz[4], out);
+}
+
+int srt_query_destroy(srt_query* q) {
+  if (!q) return SRT_ERR_INVALID;
+  (void)hipSetDevice(q->device);
+  if (q->stream) (void)hipStreamSynchronize(q->stream);
+  FreeAll(q);
+  delete q;
+  return SRT_OK;
+}
+
+int srt_query_set_bvh_count(srt_query* q, uint32_t bvh_count) {
+  if (!q) return SRT_ERR_INVALID;
+  q->bvh_count = bvh_count;
+  return SRT_OK;
+}
+
+int srt_query_update_model_matrix(srt_query* q, uint32_t index, const float frame[16]) {
+  if (!q || !frame) return SRT_ERR_INVALID;
+  if (index >= q->n_bvhs) {
+    srt::SetError("UpdateModelMatrix: index out of range");
+    return SRT_ERR_INVALID;
+  }
+  QHIP_OK(hipSetDevice(q->device));
+  // ordered with the queries on the stream; the 64 B leave `frame` before the call returns
+  QHIP_OK(hipMemcpyAsync(q->d_frames + 16 * (size_t)index, frame, 16 * sizeof(float), hipMemcpyHostToDevice, q->stream));
+  return SRT_OK;
+}
+
+int srt_query_closest(srt_query* q, const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
+  return Launch<false>(q, rays_dev, n, hits_dev);
+}
+
+int srt_query_occluded(srt_query* q, const srt_ray* rays_dev, uint32_t n, uint8_t* occluded_dev) {
+  return Launch<true>(q, rays_dev, n, occluded_dev);
+}
+
+int srt_query_get_int(srt_query* q, const char* name, int* v) {
+  if (!q || !name || !v) return SRT_ERR_INVALID;
+  const std::string n(name);
+  if (n == "stack.entries") *v = q->plan.entries;
+  else if (n == "stack.in_hbm") *v = q->plan.in_hbm ? 1 : 0;
+  else if (n == "stack.packed") *v = q->plan.packed ? 1 : 0;
+  else if (n == "launch.blocks") *v = q->last_blocks;
+  else if (n == "launch.block") *v = kBlock;
+  else if (n == "scratch.bytes") *v = (int)std::min<size_t>(0x7FFFFFFF, 256 + q->plan.hbm_block_bytes * (size_t)q->stack_blocks);
+  else if (n == "scene.bytes") *v = (int)std::min<size_t>(0x7FFFFFFF, q->scene_bytes);
+  else if (n == "refill.min") *v = q->refill_min;
+  else if (n == "bvh_count") *v = (int)q->bvh_count;
+  else return SRT_ERR_NOT_FOUND;
+  return SRT_OK;
+}
+
+void* srt_query_stream(srt_query* q) { return q ? q->stream : nullptr; }
+
+}  // extern "C"

@@ -79,6 +79,13 @@ class Texture(C.Structure):
     _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32)]
 
 
+class Hit(C.Structure):
+    """srt_hit (include/srt_query.h)."""
+    _fields_ = [("triangle", C.c_uint32), ("t", C.c_float), ("normal", C.c_float * 3), ("material", C.c_uint32),
+                ("bvh", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(Hit) == 32
 assert C.sizeof(BvhRecord) == 80 and C.sizeof(BvhNode) == 32 and C.sizeof(MaterialObj) == 48
 assert C.sizeof(Triangle) == 16 and C.sizeof(Vertex) == 32 and C.sizeof(Light) == 32 and C.sizeof(Ray) == 32
 
@@ -179,6 +186,22 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
+# include/srt_query.h: the ray-query service (its own header and version; srt_amd.h's table above is unchanged)
+_QUERY_SIGS = {
+    "srt_query_abi_version": (C.c_int, []),
+    "srt_query_create": (C.c_int, [C.c_int, P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32,
+                                   C.POINTER(P)]),
+    "srt_query_create_obj": (C.c_int, [C.c_int, P, P, C.POINTER(P)]),
+    "srt_query_destroy": (C.c_int, [P]),
+    "srt_query_set_bvh_count": (C.c_int, [P, C.c_uint32]),
+    "srt_query_update_model_matrix": (C.c_int, [P, C.c_uint32, P]),
+    "srt_query_closest": (C.c_int, [P, P, C.c_uint32, P]),
+    "srt_query_occluded": (C.c_int, [P, P, C.c_uint32, P]),
+    "srt_query_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_query_stream": (P, [P]),
+}
+QUERY_SYMBOLS = tuple(_QUERY_SIGS)
+
 _lib = None
 
 
@@ -207,6 +230,10 @@ def lib() -> C.CDLL:
                 pass
         handle = C.CDLL(str(LIB_PATH), mode=os.RTLD_NOW | C.RTLD_GLOBAL)
         for name, (res, args) in _SIGS.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in _QUERY_SIGS.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,181 @@
+"""Device-resident batched ray queries (include/srt_query.h): closest hit and occlusion.
+
+``Query(scene)`` uploads a copy of the scene to the device; ``closest(rays)`` and ``occluded(rays)`` trace a
+``torch`` tensor of rays that already lives there and return device tensors, without a host round trip or a
+synchronisation.  The results are bit-identical to the CPU oracle's ``trace_closest``.  A numpy structured
+array of ``RAY_DTYPE`` is accepted too; that path copies both ways and synchronises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import RAY_DTYPE, Scene, _ptr
+from ._lib import check, lib
+
+__all__ = ["Query", "Hits", "HIT_DTYPE", "MISS"]
+
+MISS = 0xFFFFFFFF
+# srt_hit, 32 B
+HIT_DTYPE = np.dtype([("triangle", "<u4"), ("t", "<f4"), ("normal", "<f4", 3), ("material", "<u4"), ("bvh", "<u4"),
+                      ("pad", "<u4")])
+assert HIT_DTYPE.itemsize == 32
+
+
+class Hits:
+    """``srt_hit`` records on the device: ``raw`` is the ``[n, 8]`` int32 storage, the properties view its
+    fields (no copies).  ``triangle`` is int32, so a miss (0xFFFFFFFF) reads -1; ``hit`` is the boolean mask."""
+
+    def __init__(self, raw):
+        self.raw = raw
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    @property
+    def triangle(self):
+        return self.raw[:, 0]
+
+    @property
+    def hit(self):
+        return self.raw[:, 0] != -1
+
+    @property
+    def t(self):
+        import torch
+        return self.raw[:, 1].view(torch.float32)
+
+    @property
+    def normal(self):
+        import torch
+        return self.raw[:, 2:5].view(torch.float32)
+
+    @property
+    def material(self):
+        return self.raw[:, 5]
+
+    @property
+    def bvh(self):
+        return self.raw[:, 6]
+
+    def numpy(self) -> np.ndarray:
+        """The records on the host as a ``HIT_DTYPE`` array (copies and synchronises)."""
+        return self.raw.cpu().numpy().view(HIT_DTYPE).reshape(-1)
+
+
+class Query:
+    """A ray-query object over ``scene`` (a :class:`srt_amd.Scene`) on ``device``.
+
+    ``stream``: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` handle the queries run on.  With the default
+    (None) the object runs on a stream of its own and orders every call with ``torch.cuda.current_stream()``
+    by events -- the call waits for the work already queued there, and that stream waits for the results -- so
+    it behaves as if it ran on the current stream, whichever that is at the time of the call.
+    """
+
+    def __init__(self, scene: Scene, device: int = 0, stream=None):
+        self.device = int(device)
+        self._q = None
+        self._ext = None
+        handle = getattr(stream, "cuda_stream", stream)
+        self._own_stream = not handle
+        h = C.c_void_p()
+        s = scene
+        check(lib().srt_query_create(self.device, C.c_void_p(handle) if handle else None, _ptr(s.bvhs), len(s.bvhs),
+                                     _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
+                                     len(s.verts), C.byref(h)), "srt_query_create")
+        self._q = h
+
+    # -- lifecycle ------------------------------------------------------------
+    def close(self):
+        if self._q is not None:
+            lib().srt_query_destroy(self._q)
+            self._q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        if self._q is None:
+            raise RuntimeError("Query is closed")
+        return self._q
+
+    # -- state ----------------------------------------------------------------
+    def set_bvh_count(self, bvh_count: int):
+        check(lib().srt_query_set_bvh_count(self.handle, int(bvh_count)), "srt_query_set_bvh_count")
+
+    def update_model_matrix(self, index: int, matrix):
+        """``AssetUtils::UpdateModelMatrix``; ``matrix`` is glm column-major (m[c][r])."""
+        m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4)).reshape(16)
+        check(lib().srt_query_update_model_matrix(self.handle, int(index), _ptr(m)), "srt_query_update_model_matrix")
+
+    def get_int(self, name: str) -> int:
+        v = C.c_int()
+        check(lib().srt_query_get_int(self.handle, name.encode(), C.byref(v)), f"srt_query_get_int({name})")
+        return v.value
+
+    # -- queries --------------------------------------------------------------
+    def _ordered(self, torch):
+        """The library's own stream as a torch stream (default-stream mode), else None."""
+        if not self._own_stream:
+            return None
+        if self._ext is None:
+            self._ext = torch.cuda.ExternalStream(int(lib().srt_query_stream(self.handle)), device=self.device)
+        return self._ext
+
+    def _check_rays(self, torch, rays):
+        if (rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
+                or not rays.is_cuda or rays.device.index != self.device):
+            raise ValueError(f"rays must be a contiguous float32 [n, 8] tensor on cuda:{self.device} (srt_ray fields)")
+
+    def _run(self, fn, what, rays, out):
+        import torch
+        ext = self._ordered(torch)
+        cur = torch.cuda.current_stream(self.device) if ext is not None else None
+        if ext is not None:
+            ext.wait_stream(cur)
+        check(fn(self.handle, C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr())), what)
+        if ext is not None:
+            cur.wait_stream(ext)
+        return out
+
+    def closest(self, rays):
+        """Closest hits of ``rays``: a :class:`Hits` over a device tensor (torch input), or a ``HIT_DTYPE``
+        array (numpy ``RAY_DTYPE`` input)."""
+        import torch
+        if isinstance(rays, np.ndarray):
+            dev = torch.from_numpy(np.ascontiguousarray(rays, dtype=RAY_DTYPE).view(np.float32).reshape(-1, 8))
+            hits = self.closest(dev.to(f"cuda:{self.device}"))
+            self.synchronize()
+            return hits.numpy()
+        self._check_rays(torch, rays)
+        out = torch.empty((rays.shape[0], 8), dtype=torch.int32, device=rays.device)
+        return Hits(self._run(lib().srt_query_closest, "srt_query_closest", rays, out))
+
+    def occluded(self, rays):
+        """1 where some triangle is accepted (the walk stops at the first): a uint8 ``[n]`` device tensor, or
+        a numpy array for numpy input."""
+        import torch
+        if isinstance(rays, np.ndarray):
+            dev = torch.from_numpy(np.ascontiguousarray(rays, dtype=RAY_DTYPE).view(np.float32).reshape(-1, 8))
+            occ = self.occluded(dev.to(f"cuda:{self.device}"))
+            self.synchronize()
+            return occ.cpu().numpy()
+        self._check_rays(torch, rays)
+        out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+        return self._run(lib().srt_query_occluded, "srt_query_occluded", rays, out)
+
+    def synchronize(self):
+        """Wait for the queries enqueued so far."""
+        import torch
+        torch.cuda.ExternalStream(int(lib().srt_query_stream(self.handle) or 0), device=self.device).synchronize()
