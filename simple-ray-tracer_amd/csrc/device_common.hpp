@@ -41,7 +41,7 @@ struct KParams {
   int nodes_f4, tris_f4;   // LDS-resident scene: sizes of the node / triangle arrays in float4
   int nodes_lds_f4;        // LDS mode: float4 the node copy occupies (pair blocks padded, traversal.hpp node_lds_f4)
   // internal nodes' child index: pairs start at odd slots and an even index (the
-  // pair's start - 1) flags a right child whose own pair follows (pathtrace.hip
+  // pair's start - 1) flags a right child whose own pair follows (scene_layout.cpp
   // LayoutNodes); ref_or = 1 decodes it, 0 for the identity layout (no flags)
   uint32_t ref_or;
   float4* lbuf;            // sample buffer: nframes x local_pixels radiance samples
@@ -56,7 +56,7 @@ struct KParams {
   int stack_base_f4;       // first float4 of the per-lane stacks in dynamic LDS
   int coop_off;            // global-scene mode, SRT_COOP: LDS byte offset of the waves' load stages (traversal.hpp)
   // global-scene mode, fused instance: the node array's first top_f4 float4 (the top levels' pairs,
-  // pathtrace.hip LayoutNodes) copied into each block's LDS at float4 top_lds_f4 (padded pair blocks,
+  // scene_layout.cpp LayoutNodes) copied into each block's LDS at float4 top_lds_f4 (padded pair blocks,
   // node_lds_f4); 0: none
   int top_f4, top_lds_f4;
   uint32_t* gstack;        // global-scene mode: per-lane stacks in HBM, entry field k of lane g at gstack[k * stride + g]
@@ -81,15 +81,7 @@ struct KParams {
 // Dynamic LDS of the path-tracing kernels: [scene copy (LDS mode)] [per-lane stacks].
 extern __shared__ __attribute__((aligned(16))) float4 g_smem[];
 
-enum { ST_RAYS = 0, ST_NODES, ST_TRIS, ST_RNGU, ST_RNGSQ, ST_LIGHTS, ST_MATS, ST_SAMPLES, ST_OVERFLOW, ST_MAXSTACK,
-       ST_BOUNCECAP,  // paths cut at the bounce cap (KParams::bounce_cap)
-       ST_SHADOW,     // shadow rays among ST_RAYS (CheckLightOccluded, raytrace_compute.glsl:167-176)
-       ST_N, ST_CYC_REFILL = ST_N, ST_CYC_TRAV, ST_CYC_SHADE, ST_CYC_ITERS,
-       // lane occupancy of the traversal loop (summed popcounts per iteration) and of shading
-       ST_DBG_TITERS, ST_DBG_WORK, ST_DBG_TRAV, ST_DBG_LEAF, ST_DBG_INT, ST_DBG_SHADE,
-       // per traversal sub-step k < 16: lanes taking it (summed), waves executing it, lanes popping after it
-       ST_DBG_SUB, ST_POOLERR = ST_DBG_SUB + 48,  // pool_kernel's watchdog fired (pool.hpp)
-       ST_TOTAL };
+// (the ST_* indices of the launch statistics: srt_internal.hpp, the host files size the array by them)
 // SRT_PHASE_TIMING builds, in the last two sub-steps' slots (no pattern has 15 sub-steps): traversing lanes
 // summed per traversal iteration by ray kind (shadow, camera, bounce), and ray starts by kind (camera,
 // shadow, bounce)

@@ -316,7 +316,7 @@ __device__ __forceinline__ void sample_body(const KParams& kp) {
   // broadcast, when needed).  From kp.tail_start on (16 claims per wave
   // before the end, pathtrace.hip) a claim takes one batch: a wave then holds
   // at most two batches, so the launch's tail is not set by slow waves still
-  // draining several expensive batches each (tools/wave_trace.py).
+  // draining several expensive batches each (tools/probes/wave_trace.py).
   // `batch` and everything derived from it are wave-uniform (scalar
   // registers); the counter's overshoot past n_batches stays below 2^31.
   // The sphere scene's batches are cheap and take kClaimSph per claim.

@@ -1,5 +1,6 @@
-// pathtrace.hip -- the device context behind the C ABI: scene / noise / light
-// uploads, image buffers, launches of the kernels in kernels.hpp, statistics.
+// pathtrace.hip -- the kernel-launching part of the device context behind the C ABI (context.hpp): scene
+// and texture uploads, launches of the kernels in kernels.hpp.  context.cpp holds the host-only part,
+// scene_layout.cpp the validation and the node / triangle layouts the upload writes.
 //
 // Kernels (kernels.hpp; DESIGN.md sections 4-5):
 //   sample_kernel      persistent: waves claim 64-item batches (an 8x8 tile of
@@ -19,9 +20,7 @@
 //            padded with kTriPad zero records;
 //   mats   : 32 B shading material (albedo|roughness, specular) precomputed
 //            from MaterialFromOBJ (raytrace_utils.glsl:140-175);
-//   lights : 32 B, one zero record appended (lights[lightCount] reads zero);
-//   noise  : noiseTex as .xy float2 (8 B), noiseUniformTex as .x float (4 B):
-//            the only channels the kernel reads.
+//   lights, noise: context.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,253 +28,23 @@
 #include <cstdio>
 #include <cstddef>
 #include <cstring>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
-
-#include <zlib.h>
 
 #include "kernels.hpp"
 #include "pool.hpp"
 #include "wavefront.hpp"
 
+#include "context.hpp"
+#include "scene_layout.hpp"
+
 // ===========================================================================
-// host side: the device context behind the C ABI
+// host side: the launches behind the C ABI
 // ===========================================================================
-namespace srt {
-
-static std::mutex g_err_mu;
-static std::string g_err;
-void SetError(const std::string& msg) {
-  std::lock_guard<std::mutex> lk(g_err_mu);
-  g_err = msg;
-}
-const char* LastError() {
-  std::lock_guard<std::mutex> lk(g_err_mu);
-  return g_err.c_str();
-}
-
-}  // namespace srt
-
-#define HIP_OK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
-      return SRT_ERR_HIP;                                                                     \
-    }                                                                                         \
-  } while (0)
-
-struct srt_context {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // uniforms
-  int W = 0, H = 0, accum_frames = 0, reset = 0, show_model = 0, light_count = 0, max_depth = 5;
-  uint32_t bvh_count = 0;
-  float cam_origin[3] = {0, 0, 0}, cam_dir[3] = {0, 0, -1}, cam_up[3] = {0, 1, 0}, cam_right[3] = {1, 0, 0};
-  // tiling
-  int rank = 0, nranks = 1, band_rows = 16;
-  // scene
-  float4* d_nodes = nullptr;
-  float4* d_tris = nullptr;
-  float4* d_mats = nullptr;
-  srt_bvh_record* d_bvhs = nullptr;
-  uint32_t bvh_capacity = 0;
-  uint32_t bvh_uploaded = 0;   // records on the device (valid while !bvhs_dirty)
-  bool bvhs_dirty = true;
-  std::vector<srt_bvh_record> h_bvhs;
-  std::vector<std::pair<uint32_t, uint32_t>> bvh_tris;  // triangle range [lo, hi) of each record's tree
-  uint32_t n_nodes = 0, n_tris = 0, n_mats = 0;
-  uint32_t ref_or = 0;  // KParams::ref_or of the uploaded node layout
-  // textures (srt_upload_textures) and, when materials sample them, the
-  // per-triangle vertex uvs (2 float4: uv0 uv1 | uv2 0 0)
-  void* d_tex = nullptr;         // texels: RGBA8 (SRT_TEX8) or RGBA32F
-  uint4* d_tex_info = nullptr;  // first texel, width, height, 0
-  uint32_t n_tex = 0;
-  float4* d_tri_uv = nullptr;
-  bool sample_textures = false;
-  int stack_entries = 1;
-  bool scene_ok = false;
-  bool lds_ok = false;        // scene indices fit the packed LDS stack entry
-  bool pairs_aligned = false; // every internal node's child pair starts at an odd slot (LDS mode's node_pair)
-  bool force_global = false;  // SRT_FORCE_GLOBAL_SCENE=1 disables LDS mode
-  bool fused = false;         // global-scene mode's fused sub-steps (set at upload: trees the Infinity Cache holds)
-  int top_f4 = 0, top_depth = 0;  // the node array's top-level region (LayoutNodes) the fused instance copies to LDS
-  int launch_top_f4 = 0;           // the region the last global-scene launch copied (0: none)
-  bool launch_overlap = false;     // the last render's sample launches ran piped and overlapped (launch.overlap)
-  int launch_per_cu = 0, launch_block = 0;  // resident blocks per CU and lanes per block of the last sample launch
-  int launch_mats_lds = 0;                  // the last launch read the material records from LDS
-  int global_waves = 4;       // the fused instance's waves per SIMD (set at upload: 5 for small trees)
-  // lights
-  std::vector<srt_light> h_lights;
-  float4* d_lights = nullptr;
-  uint32_t light_capacity = 0;
-  bool lights_dirty = true;
-  // noise
-  float2* d_noise_xy = nullptr;
-  float* d_noise_u = nullptr;
-  size_t noise_texels = 0;
-  // images
-  float4* d_accum = nullptr;
-  uint32_t* d_out = nullptr;
-  bool images_external = false;
-  int img_w = 0, img_rows = 0;
-  // sample buffer (nframes x local pixels float4)
-  float4* d_lbuf = nullptr;
-  uint32_t* d_gstack = nullptr;  // global-scene mode traversal stacks
-  size_t gstack_bytes = 0;
-  // tile schedule: per-tile costs recorded by the last launch and the next
-  // launch's order (order_tiles_kernel); costs_for = the tile count they describe
-  uint32_t* d_tile_cost = nullptr;
-  uint32_t* d_tile_order = nullptr;
-  int tile_cap = 0, tile_costs_for = -1;
-  bool tile_schedule = true;  // SRT_TILE_ORDER=0: natural tile order
-  int* d_row_map = nullptr;           // nranks > 1: global row of each local row (KParams::row_map)
-  long long row_map_key = -1;         // the (rank, nranks, band_rows, rows) it was built for
-  unsigned long long* d_batch_ctr = nullptr;  // one batch counter per chunk launch
-  int batch_ctr_cap = 0;
-  size_t lbuf_bytes = 0;
-  // SRT_SAMPLE_BUFFER_MB: every sample buffer of the context together (its own, used by counting and
-  // unpipelined launches, and one per pipeline slot), split equally: 21 GiB each with the 2 default slots
-  size_t lbuf_total = (size_t)64 << 30;
-  int tail_claims = 16;  // SRT_TAIL_CLAIMS: claims per wave before the end from which claims take one batch
-  int tail_claims_gw5 = 8;  // the untextured fused 5-wave instance's (torus knot +1.4% against 16 with two slots;
-                            // the textured Airplane material loses 0.6% and keeps 16;
-                            // profiles/r05_experiments/tail_window_overlap.txt); SRT_TAIL_CLAIMS sets it too
-  int tail_claims_sph = 1;  // the sphere launch's (C2, 8 per claim: tail 16 6.20 ms, 1 3.17 ms; its batches
-                            // are cheap, the counter's atomic rate bounds it); SRT_TAIL_CLAIMS sets both
-  int trav_frac16 = 9;                 // SRT_TRAV_FRAC16 (measured best on Rubik 1080p with the 16-sub-step pattern)
-  int bounce_cap = 1 << 20;            // SRT_BOUNCE_CAP: bounces after which a path is cut (counted)
-  int trav_frac16_global = 9;          // SRT_TRAV_FRAC16_GLOBAL: the same threshold for global-scene mode
-  bool trav_frac16_global_env = false; // (set: every global instance uses it; else the fused 4-wave one takes 7, the timed IL one 8)
-  bool pool_launched = false;          // the last render ran pool_kernel (srt_finish checks its watchdog)
-  int pool = 0;                        // SRT_POOL=1: LDS mode runs pool_kernel (workgroup ray pools)
-  int pool_batch = 64;                 // SRT_POOL_BATCH: queued hits a shading wave waits for
-  int pool_tlow = 32;                  // SRT_POOL_TLOW: trace + spare records under which shading waves take fewer
-  int pool_slots_max = 4096;           // SRT_POOL_SLOTS: at most this many records
-  int pool_deadline_ms = 30000;        // SRT_POOL_DEADLINE_MS: pool_kernel's watchdog
-  int num_cus = 256;
-  int sphere_blocks = 5;               // SRT_SPHERE_BLOCKS: sphere_kernel blocks per CU (at most)
-  // wavefront mode (wavefront.hpp): global-scene launches through wf_logic / wf_shade / wf_trace
-  int wavefront = -1;                  // SRT_WAVEFRONT=1/0 forces it on / off; -1: by scene (wf_scene)
-  bool wf_scene = false;               // chosen at upload
-  uint32_t wf_slots = 1u << 21;        // SRT_WF_SLOTS: path slots in HBM
-  int wf_waves = 6;                    // SRT_WF_WAVES: waves per SIMD of wf_trace_kernel (4, 5, 6 or 8)
-  float4* d_wf_rec = nullptr;
-  uint2* d_wf_res = nullptr;
-  uint32_t *d_wf_state = nullptr, *d_wf_rayq = nullptr, *d_wf_hitq = nullptr, *d_wf_ctl = nullptr,
-           *d_wf_items = nullptr;
-  uint32_t wf_cap = 0;
-  uint32_t* h_wf_poll = nullptr;       // pinned: (live, items) of two polled iterations
-  hipEvent_t wf_poll_ev[2] = {nullptr, nullptr};
-  bool wf_launched = false;            // the last render went through wavefront mode
-  // treelet scheduling of wavefront mode's trace stage (wavefront.hpp wf_top_kernel / wf_bottom_kernel)
-  int treelets = -1;                   // SRT_TREELETS=1/0 forces it on / off; -1: by scene (tl_scene)
-  bool tl_scene = false;               // chosen at upload
-  int treelet_depth = 0;               // SRT_TREELET_DEPTH: depth of the treelet roots (0: by scene size)
-  uint32_t n_treelets = 0;             // of the uploaded scene (0: no flagged copy)
-  float4* d_nodes_t = nullptr;         // the node array with treelet roots flagged
-  uint32_t* d_troot = nullptr;         // per treelet: its root's child index
-  float4* d_tl_ray = nullptr;
-  uint32_t *d_tl_stk = nullptr, *d_tl_slist = nullptr, *d_tl_skey = nullptr, *d_tl_blist = nullptr,
-           *d_tl_rlist = nullptr, *d_tl_count = nullptr, *d_tl_fill = nullptr;
-  uint32_t tl_cap = 0, tl_count_cap = 0;
-  // stats
-  unsigned long long* d_stats = nullptr;
-  unsigned long long* d_nan = nullptr;  // NaN path samples since the last srt_reset_stats
-  srt_stats stats{};
-  uint64_t shadow_rays = 0;  // of stats.rays (srt_ray_kinds)
-  // per-chunk HIP events around the sample kernel of the last render call
-  std::vector<hipEvent_t> ev;
-  struct Occupancy {
-    const void* fn;
-    size_t lds;
-    int per_cu;
-  };
-  std::vector<Occupancy> occupancy;  // resident blocks per CU of each sample_kernel instance
-#ifdef SRT_WAVE_TRACE
-  unsigned long long* d_trace = nullptr;
-  size_t trace_bytes = 0;
-  int trace_waves = 0;
-#endif
-  int ev_used = 0;
-  // Pipelined sample launches (SRT_PIPELINE slots, default 3; 1: every launch on `stream`).  A timed
-  // sample_kernel / sphere_kernel launch goes on the next slot's own stream with the slot's sample
-  // buffer, batch counter, tile order and stacks; its accumulate_kernel stays on `stream` behind it.  A
-  // slot's next launch waits only for that slot's last accumulation, so launch k+1 fills the CUs that
-  // launch k's last waves leave idle (the drain) and the accumulations run beside them, instead of
-  // sample and accumulate alternating on one stream.  The tile order of a slot's launch comes from the
-  // costs of that slot's previous launch (the order decides which wave traces which sample, never a
-  // value).  Counting, pool and wavefront launches run on `stream` with the context's own buffers.
-  struct Slot {
-    hipStream_t stream = nullptr;
-    hipEvent_t sampled = nullptr, accumulated = nullptr;
-    bool pending = false;  // `accumulated` recorded since the slot's buffers were last known idle
-    float4* lbuf = nullptr;
-    size_t lbuf_bytes = 0;
-    unsigned long long* batch_ctr = nullptr;
-    int batch_ctr_cap = 0;
-    uint32_t* tile_cost = nullptr;
-    uint32_t* tile_order = nullptr;
-    int tile_cap = 0, tile_costs_for = -1;
-    uint32_t* gstack = nullptr;
-    size_t gstack_bytes = 0;
-  };
-  std::vector<Slot> slots;
-  // SRT_PIPELINE: launch slots, each its own stream and buffers.  Two, since launches overlap: a third slot's
-  // stream shares one of the process's 4 hardware queues (GPU_MAX_HW_QUEUES) with another, which serialises
-  // them (C2 52 -> 57 G rays/s, torus knot +2.8%, metric +0.2% with 2)
-  int pipe = 2;
-  // SRT_PIPELINE_OVERLAP: whether a sample launch may start before the previous one ends (2, the default:
-  // always; 1: on a rank's share of a multi-GPU split (nranks > 1) only; 0: never).  An overlapped launch's
-  // dispatch-to-end time (rocprofv3) and span include its wait for the CUs other launches hold, so kernel
-  // time is the union of the launches' spans (srt_kernel_time; tools/trace_intervals.py takes the same
-  // union over rocprofv3's kernel trace).
-  int pipe_overlap = 2;
-  hipEvent_t last_sampled = nullptr;  // the last sample launch's end (a slot's `sampled`, or plain_done)
-  hipEvent_t plain_done = nullptr;    // recorded on `stream` after a launch outside the slots
-  unsigned long long pipe_seq = 0;
-  hipStream_t lstream = nullptr;   // the stream the current launch's sample kernel goes on
-  // Kernel time of sample_kernel / sphere_kernel launches: each writes its span (first wave's start,
-  // last wave's end; s_memrealtime) into a record of this ring (HIP events around a pipelined launch
-  // would also time its wait for the CUs its predecessor still holds).
-  unsigned long long* d_span = nullptr;
-  static constexpr int kSpanCap = 4096;
-  unsigned long long span_seq = 0, span_read = 0;  // records written / summed by srt_kernel_time
-  unsigned long long span_done = 0;                 // the latest end srt_kernel_time has counted (a tick)
-  std::vector<long long> chunk_span;               // per chunk of the last render: its record (or -1)
-  hipEvent_t lidle = nullptr;      // synchronized before the current launch frees a launch buffer
-  hipEvent_t lidle2 = nullptr;     // (and this: the previous launch, for the buffers launches in series share)
-};
+using srt::EnsureBvhs, srt::EnsureLights, srt::FreeDev, srt::HipFail, srt::LocalRows, srt::Quiesce, srt::WaitLaunchIdle;
+using srt::LayoutNodes, srt::LayoutTris, srt::TopRegionSlots, srt::ValidateNodes;
 
 namespace {
-
-void FreeDev(void* p) {
-  if (p) (void)hipFree(p);
-}
-
-int HipFail(const char* what) {
-  const hipError_t e = hipGetLastError();
-  srt::SetError(std::string(what) + ": " + hipGetErrorString(e));
-  return SRT_ERR_HIP;
-}
-
-// Waits until no pipelined sample launch is in flight: before anything rewrites or frees device data
-// those launches read (scene, lights, BVH records, noise, row map).
-int Quiesce(srt_context* c) {
-  for (auto& s : c->slots)
-    if (s.stream) HIP_OK(hipStreamSynchronize(s.stream));
-  return SRT_OK;
-}
-
-// Before the launch being set up frees one of its buffers: the launches that may still read it are done.
-int WaitLaunchIdle(srt_context* c) {
-  if (c->lidle) HIP_OK(hipEventSynchronize(c->lidle));
-  if (c->lidle2) HIP_OK(hipEventSynchronize(c->lidle2));
-  return SRT_OK;
-}
 
 // The span record of the launch being set up (kernels.hpp sample_body), initialised on its stream.
 int TakeSpan(srt_context* c, srt::KParams& kp) {
@@ -307,76 +76,6 @@ void SwapSlot(srt_context* c, srt_context::Slot& s, bool own) {
     std::swap(c->d_gstack, s.gstack);
     std::swap(c->gstack_bytes, s.gstack_bytes);
   }
-}
-
-int LocalRows(const srt_context* c, int H) {
-  int rows = 0;
-  const int nb = (H + c->band_rows - 1) / c->band_rows;
-  for (int b = c->rank; b < nb; b += c->nranks) rows += std::min(c->band_rows, H - b * c->band_rows);
-  return rows;
-}
-
-int EnsureBvhs(srt_context* c) {
-  const uint32_t need = std::max<uint32_t>(c->bvh_count, 1);
-  if (!c->bvhs_dirty && c->bvh_uploaded >= need) return SRT_OK;
-  std::vector<srt_bvh_record> recs(need);
-  std::memset(recs.data(), 0, sizeof(srt_bvh_record) * need);   // bvhs[i >= n] read as zeros
-  for (uint32_t i = 0; i < need && i < c->h_bvhs.size(); ++i) {
-    recs[i] = c->h_bvhs[i];
-    // pad0/pad1 carry the triangle range of the record's tree, empty for a
-    // record whose frame zeroes every direction (it never hits: the ghost
-    // of src/main.cpp:683); texture sampling finds the hit's BVH by it
-    const float* f = recs[i].frame;
-    bool can_hit = false;
-    for (int k : {0, 1, 2, 4, 5, 6, 8, 9, 10}) can_hit = can_hit || f[k] != 0.0f;
-    recs[i].pad0 = can_hit ? c->bvh_tris[i].first : 0u;
-    recs[i].pad1 = can_hit ? c->bvh_tris[i].second : 0u;
-  }
-  if (c->sample_textures) {
-    for (uint32_t i = 0; i < need; ++i)
-      for (uint32_t j = 0; j < i; ++j)
-        if (recs[i].pad0 < recs[i].pad1 && recs[j].pad0 < recs[j].pad1 && recs[i].pad0 < recs[j].pad1 &&
-            recs[j].pad0 < recs[i].pad1) {
-          srt::SetError("texture sampling needs BVH records with disjoint triangle ranges");
-          return SRT_ERR_INVALID;
-        }
-  }
-  if (int rq = Quiesce(c)) return rq;
-  if (need > c->bvh_capacity) {
-    FreeDev(c->d_bvhs);
-    c->d_bvhs = nullptr;
-    HIP_OK(hipMalloc(&c->d_bvhs, sizeof(srt_bvh_record) * need));
-    c->bvh_capacity = need;
-  }
-  HIP_OK(hipMemcpyAsync(c->d_bvhs, recs.data(), sizeof(srt_bvh_record) * need, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  c->bvh_uploaded = need;
-  c->bvhs_dirty = false;
-  return SRT_OK;
-}
-
-int EnsureLights(srt_context* c) {
-  if (!c->lights_dirty) return SRT_OK;
-  // the uploaded records plus one zero record that out-of-range indices map
-  // to (lights[lightCount] is an out-of-bounds SSBO read, src/main.cpp:690)
-  const size_t n = c->h_lights.size() + 1;
-  std::vector<float4> rec(2 * n, make_float4(0, 0, 0, 0));
-  for (size_t i = 0; i < c->h_lights.size(); ++i) {
-    const srt_light& l = c->h_lights[i];
-    rec[2 * i] = make_float4(l.position[0], l.position[1], l.position[2], l.intensity);
-    rec[2 * i + 1] = make_float4(l.color[0], l.color[1], l.color[2], 0.0f);
-  }
-  if (int rq = Quiesce(c)) return rq;
-  if (n > c->light_capacity) {
-    FreeDev(c->d_lights);
-    c->d_lights = nullptr;
-    HIP_OK(hipMalloc(&c->d_lights, sizeof(float4) * 2 * n));
-    c->light_capacity = (uint32_t)n;
-  }
-  HIP_OK(hipMemcpyAsync(c->d_lights, rec.data(), sizeof(float4) * 2 * n, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  c->lights_dirty = false;
-  return SRT_OK;
 }
 
 // GetCamera (raytrace_compute.glsl:47-76) with focusDist = 1 (:384)
@@ -1177,219 +876,6 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
   return SRT_OK;
 }
 
-// Depth of each BVH (root depth 0) and index validation.
-// Every node some traversal can reach is checked: the trees of the BVH records and node 0's (the
-// ghost records past n_bvhs traverse from node 0, raytrace_compute.glsl:144-147).  `reach` marks
-// them; the layouts and the upload touch no other node, so an unreachable record may hold anything.
-int ValidateNodes(const srt_bvh_node* nodes, uint32_t n_nodes, uint32_t n_tris, const srt_bvh_record* bvhs,
-                  uint32_t n_bvhs, int* max_depth, std::vector<std::pair<uint32_t, uint32_t>>* tri_ranges,
-                  std::vector<uint8_t>* reach) {
-  *max_depth = 0;
-  tri_ranges->assign(n_bvhs, {0u, 0u});
-  reach->assign(n_nodes, 0);
-  std::vector<std::pair<uint32_t, int>> st;
-  std::vector<uint8_t> seen(n_nodes, 0);
-  for (uint32_t b = 0; b <= n_bvhs; ++b) {  // b == n_bvhs: node 0's tree
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    const uint32_t root = b < n_bvhs ? bvhs[b].first_index : 0u;
-    if (root >= n_nodes) {
-      srt::SetError("BVH first_index out of range");
-      return SRT_ERR_INVALID;
-    }
-    st.push_back({root, 0});
-    while (!st.empty()) {
-      auto [i, d] = st.back();
-      st.pop_back();
-      (*reach)[i] = 1;
-      *max_depth = std::max(*max_depth, d);
-      const srt_bvh_node& n = nodes[i];
-      if (n.prim_count > 0) {
-        if ((uint64_t)n.first_child_or_prim_index + n.prim_count > n_tris || n.prim_count >= 0x80000000u) {
-          srt::SetError("BVH leaf references triangles out of range");
-          return SRT_ERR_INVALID;
-        }
-        lo = std::min(lo, n.first_child_or_prim_index);
-        hi = std::max(hi, n.first_child_or_prim_index + n.prim_count);
-      } else {
-        if ((uint64_t)n.first_child_or_prim_index + 1 >= n_nodes || seen[i]) {
-          srt::SetError("BVH internal node references children out of range (or a cycle)");
-          return SRT_ERR_INVALID;
-        }
-        seen[i] = 1;
-        st.push_back({n.first_child_or_prim_index, d + 1});
-        st.push_back({n.first_child_or_prim_index + 1, d + 1});
-      }
-    }
-    std::fill(seen.begin(), seen.end(), 0);
-    if (b < n_bvhs) (*tri_ranges)[b] = lo < hi ? std::make_pair(lo, hi) : std::make_pair(0u, 0u);
-  }
-  return SRT_OK;
-}
-
-// Device node layout.  An internal step reads the current node's child pair
-// and, speculatively, the pair after it (traversal.hpp, trav_internal): when
-// the right child -- the one the traversal visits first -- is internal and its
-// own child pair is that next pair, the step expands it too, so a descent along
-// right children takes one memory round trip per two levels.  The device array
-// therefore holds the pairs in the traversal's order (pre-order, right child
-// first), where a right child's pair directly follows its parent's.  Only
-// addresses change: every record keeps its bounds, leaf triangle range and
-// count; an internal node's child index and each BVH's root are remapped.  Slot
-// 0 keeps node 0 (the ghost zero records traverse from it); other roots take a
-// pair's first slot with a zero record beside it.  Returns false (the identity
-// layout is used) for inputs whose sibling pairs overlap, which no
-// reference-built tree has.  A child pair reached from two BVH records' trees
-// keeps its first placement; srt_upload_scene sets a node's "right child's
-// pair follows" flag only where the remapped slots confirm it.
-// `top_depth` > 0 (global-scene scenes, SRT_TOP_DEPTH): the pairs of every node at depth < top_depth are
-// laid out first, in the same order, so they form the array's first `*n_top_slots` slots -- the region the
-// fused instance copies into each block's LDS (traversal.hpp trav_fused) -- and the rest follows.  A pair
-// on the region's last level keeps no right-spine flag (its right child's pair lies past the region).
-bool LayoutNodes(const srt_bvh_node* nodes, uint32_t n_nodes, const srt_bvh_record* bvhs, uint32_t n_bvhs,
-                 bool align, std::vector<uint32_t>* remap, uint32_t* n_slots, int top_depth = 0,
-                 uint32_t* n_top_slots = nullptr) {
-  constexpr uint32_t kUnset = 0xFFFFFFFFu;
-  remap->assign(n_nodes, kUnset);
-  auto& m = *remap;
-  m[0] = 0;
-  uint32_t next = 1;  // pairs start at odd slots (64-B aligned behind the 32-B pad)
-  std::vector<uint32_t> roots{0};
-  for (uint32_t b = 0; b < n_bvhs; ++b) {
-    const uint32_t r = bvhs[b].first_index;
-    if (m[r] == kUnset) {
-      m[r] = next;
-      next += 2;
-    }
-    roots.push_back(r);
-  }
-  // `align`: a chain of right-child pairs starts on a 128-B line (slot = 3 mod
-  // 4: a zero pair pads before it when needed), so a step that reads a pair and
-  // its right child's pair touches one line (see srt_upload_scene for when).
-  uint32_t chain_next = kUnset;  // the node whose pair continues the current chain
-  std::vector<uint8_t> top(top_depth > 0 ? n_nodes : 0, 0);  // nodes whose pair the first pass laid out
-  std::vector<std::pair<uint32_t, int>> st;                    // (node, depth)
-  for (int pass = top_depth > 0 ? 0 : 1; pass < 2; ++pass) {
-    chain_next = kUnset;
-    for (uint32_t r : roots) {
-      st.push_back({r, 0});
-      while (!st.empty()) {
-        const uint32_t i = st.back().first;
-        const int d = st.back().second;
-        st.pop_back();
-        const srt_bvh_node& n = nodes[i];
-        if (n.prim_count > 0) continue;
-        const uint32_t c0 = n.first_child_or_prim_index, c1 = c0 + 1;
-        if (pass == 1 && !top.empty() && top[i]) {  // laid out by the first pass: descend only
-          st.push_back({c0, d + 1});
-          st.push_back({c1, d + 1});
-          continue;
-        }
-        if (pass == 0 && d >= top_depth) continue;
-        if (m[c0] == kUnset && m[c1] == kUnset) {
-          if (align && i != chain_next && nodes[c1].prim_count == 0 && (next & 3u) != 3u) next += 2;
-          m[c0] = next;
-          m[c1] = next + 1;
-          next += 2;
-          if (pass == 0) top[i] = 1;
-          chain_next = nodes[c1].prim_count == 0 ? c1 : kUnset;
-          st.push_back({c0, d + 1});  // popped after c1's subtree: c1 is visited first
-          st.push_back({c1, d + 1});
-        } else if (m[c0] == kUnset || m[c1] != m[c0] + 1) {
-          return false;  // a shared or overlapping pair
-        }
-      }
-    }
-    if (pass == 0 && n_top_slots) *n_top_slots = next;
-  }
-  if (top_depth <= 0 && n_top_slots) *n_top_slots = 0;
-  *n_slots = next;
-  return true;
-}
-
-// The slots LayoutNodes(..., top_depth) gives its top region: its first pass alone (the pairs of the nodes
-// at depth < top_depth, bounded by the depth, not the tree's size); false where LayoutNodes would fail.
-bool TopRegionSlots(const srt_bvh_node* nodes, uint32_t n_nodes, const srt_bvh_record* bvhs, uint32_t n_bvhs,
-                    bool align, int top_depth, uint32_t* n_top) {
-  std::unordered_map<uint32_t, uint32_t> m;  // the few nodes the pass places -> slot
-  m[0] = 0;
-  uint32_t next = 1;
-  std::vector<uint32_t> roots{0};
-  for (uint32_t b = 0; b < n_bvhs; ++b) {
-    const uint32_t r = bvhs[b].first_index;
-    if (!m.count(r)) {
-      m[r] = next;
-      next += 2;
-    }
-    roots.push_back(r);
-  }
-  constexpr uint32_t kUnset = 0xFFFFFFFFu;
-  uint32_t chain_next = kUnset;
-  std::vector<std::pair<uint32_t, int>> st;
-  for (uint32_t r : roots) {
-    st.push_back({r, 0});
-    while (!st.empty()) {
-      const uint32_t i = st.back().first;
-      const int d = st.back().second;
-      st.pop_back();
-      const srt_bvh_node& n = nodes[i];
-      if (n.prim_count > 0 || d >= top_depth) continue;
-      const uint32_t c0 = n.first_child_or_prim_index, c1 = c0 + 1;
-      const auto f0 = m.find(c0), f1 = m.find(c1);
-      if (f0 == m.end() && f1 == m.end()) {
-        if (align && i != chain_next && nodes[c1].prim_count == 0 && (next & 3u) != 3u) next += 2;
-        m[c0] = next;
-        m[c1] = next + 1;
-        next += 2;
-        chain_next = nodes[c1].prim_count == 0 ? c1 : kUnset;
-        st.push_back({c0, d + 1});
-        st.push_back({c1, d + 1});
-      } else if (f0 == m.end() || f1 == m.end() || f1->second != f0->second + 1) {
-        return false;
-      }
-    }
-  }
-  *n_top = next;
-  return true;
-}
-
-// Device triangle slots for scenes read through L2 (global-scene mode).  A leaf
-// of one or two triangles (the midpoint builder's leaves on a triangle soup) is
-// read by one leaf step; at 48 B per record, 5 of every 8 such reads straddle
-// two 128-B lines.  Here each such leaf starts at a slot whose records
-// lie in one line (slot mod 8 in {0, 1, 3, 4, 6, 7} for one record, {0, 3, 6}
-// for two), zero records filling the gaps; larger leaves are not padded.  The
-// map is monotone, so the order is kept and a BVH's triangle range stays one
-// slot range.  Returns false (identity) when two leaves' ranges partly overlap.
-bool LayoutTris(const srt_bvh_node* nodes, uint32_t n_nodes, const std::vector<uint8_t>& reach, uint32_t n_tris,
-                std::vector<uint32_t>* slot, uint32_t* n_slots) {
-  constexpr uint32_t kUnset = 0xFFFFFFFFu;
-  std::vector<uint32_t> owner(n_tris, kUnset), lead(n_tris, 0);
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    const srt_bvh_node& n = nodes[i];
-    if (n.prim_count == 0 || !reach[i]) continue;  // (ValidateNodes range-checked the reachable leaves)
-    const uint32_t f = n.first_child_or_prim_index;
-    if (lead[f] != 0 && lead[f] != n.prim_count) return false;  // two leaves from one triangle, different sizes
-    if (lead[f] == n.prim_count) continue;                      // the same leaf again (a shared subtree)
-    for (uint32_t t = f; t < f + n.prim_count; ++t) {
-      if (owner[t] != kUnset) return false;
-      owner[t] = f;
-    }
-    lead[f] = n.prim_count;
-  }
-  slot->resize(n_tris);
-  uint32_t s = 0;
-  for (uint32_t t = 0; t < n_tris; ++t) {
-    if (lead[t] == 1) {
-      while ((s & 7u) == 2u || (s & 7u) == 5u) ++s;
-    } else if (lead[t] == 2) {
-      while ((s & 7u) % 3u != 0u) ++s;  // {0, 3, 6}
-    }
-    (*slot)[t] = s++;
-  }
-  *n_slots = s;
-  return true;
-}
-
 }  // namespace
 
 namespace srt {
@@ -1423,219 +909,17 @@ int AssembleOutputOn(srt_context* c, void* stream, const void* gathered_rgba8, i
   return SRT_OK;
 }
 
-int DetachImages(srt_context* c) {
-  if (!c) return SRT_ERR_INVALID;
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  if (int rq = Quiesce(c)) return rq;
-  if (!c->images_external) { FreeDev(c->d_accum); FreeDev(c->d_out); }
-  c->d_accum = nullptr;
-  c->d_out = nullptr;
-  c->images_external = false;
-  c->img_w = c->img_rows = 0;
-  c->rank = 0;
-  c->nranks = 1;
-  return SRT_OK;
-}
-
 }  // namespace srt
 
 // ===========================================================================
-// C ABI (context part)
+// C ABI (launch part; context.cpp holds the rest)
 // ===========================================================================
 extern "C" {
 
-const char* srt_last_error(void) { return srt::LastError(); }
-int srt_abi_version(void) { return SRT_ABI_VERSION; }
 #ifndef SRT_CODE_HASH
 #define SRT_CODE_HASH "unknown"
 #endif
 const char* srt_code_hash(void) { return SRT_CODE_HASH; }
-
-int srt_create(int device, void* stream, srt_context** out) {
-  if (!out) return SRT_ERR_INVALID;
-  HIP_OK(hipSetDevice(device));
-  auto* c = new srt_context();
-  c->device = device;
-  if (const char* e = std::getenv("SRT_FORCE_GLOBAL_SCENE")) c->force_global = e[0] == '1';
-  if (const char* e = std::getenv("SRT_SAMPLE_BUFFER_MB")) c->lbuf_total = (size_t)std::max(1L, std::atol(e)) << 20;
-  if (const char* e = std::getenv("SRT_SAMPLE_BUFFER_KB")) c->lbuf_total = (size_t)std::max(1L, std::atol(e)) << 10;
-  if (const char* e = std::getenv("SRT_BOUNCE_CAP")) c->bounce_cap = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("SRT_POOL")) c->pool = e[0] == '1';
-  if (const char* e = std::getenv("SRT_POOL_BATCH")) c->pool_batch = std::max(1, std::min(64, std::atoi(e)));
-  if (const char* e = std::getenv("SRT_POOL_TLOW")) c->pool_tlow = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("SRT_POOL_SLOTS")) c->pool_slots_max = std::max(64, std::atoi(e));
-  if (const char* e = std::getenv("SRT_POOL_DEADLINE_MS")) c->pool_deadline_ms = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("SRT_SPHERE_BLOCKS")) c->sphere_blocks = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("SRT_WAVEFRONT")) c->wavefront = e[0] == '1' ? 1 : 0;
-  if (const char* e = std::getenv("SRT_WF_SLOTS")) c->wf_slots = (uint32_t)std::max(256L, std::min(1L << 28, std::atol(e)));
-  if (const char* e = std::getenv("SRT_WF_WAVES")) c->wf_waves = std::atoi(e);
-  if (const char* e = std::getenv("SRT_TREELETS")) c->treelets = e[0] == '1' ? 1 : 0;
-  if (const char* e = std::getenv("SRT_TREELET_DEPTH")) c->treelet_depth = std::max(0, std::min(srt::kTopStack - 1, std::atoi(e)));
-  if (const char* e = std::getenv("SRT_PIPELINE")) c->pipe = std::max(1, std::min(8, std::atoi(e)));
-  if (const char* e = std::getenv("SRT_PIPELINE_OVERLAP")) c->pipe_overlap = std::max(0, std::min(2, std::atoi(e)));
-  if (const char* e = std::getenv("SRT_TAIL_CLAIMS"))
-    c->tail_claims = c->tail_claims_sph = c->tail_claims_gw5 = std::max(0, std::atoi(e));
-  if (const char* e = std::getenv("SRT_TILE_ORDER")) c->tile_schedule = e[0] != '0';
-  if (const char* e = std::getenv("SRT_TRAV_FRAC16")) c->trav_frac16 = std::max(0, std::min(16, std::atoi(e)));
-  if (const char* e = std::getenv("SRT_TRAV_FRAC16_GLOBAL"))
-    c->trav_frac16_global = std::max(0, std::min(16, std::atoi(e))), c->trav_frac16_global_env = true;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-      c->num_cus = prop.multiProcessorCount;
-  }
-  if (stream) {
-    c->stream = static_cast<hipStream_t>(stream);
-  } else {
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      delete c;
-      srt::SetError(std::string("hipStreamCreate: ") + hipGetErrorString(e));
-      return SRT_ERR_HIP;
-    }
-    c->own_stream = true;
-  }
-  c->lstream = c->stream;
-  if (hipMalloc(&c->d_stats, sizeof(unsigned long long) * srt::ST_TOTAL) != hipSuccess ||
-      hipMemset(c->d_stats, 0, sizeof(unsigned long long) * srt::ST_TOTAL) != hipSuccess ||
-      hipMalloc(&c->d_nan, sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(c->d_nan, 0, sizeof(unsigned long long)) != hipSuccess) {
-    FreeDev(c->d_stats);
-    FreeDev(c->d_nan);
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-    srt::SetError("hipMalloc(stats) failed");
-    return SRT_ERR_HIP;
-  }
-  *out = c;
-  return SRT_OK;
-}
-
-int srt_destroy(srt_context* c) {
-  if (!c) return SRT_ERR_INVALID;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)Quiesce(c);
-  for (auto& sl : c->slots) {
-    FreeDev(sl.lbuf); FreeDev(sl.batch_ctr); FreeDev(sl.tile_cost); FreeDev(sl.tile_order); FreeDev(sl.gstack);
-    if (sl.sampled) (void)hipEventDestroy(sl.sampled);
-    if (sl.accumulated) (void)hipEventDestroy(sl.accumulated);
-    if (sl.stream) (void)hipStreamDestroy(sl.stream);
-  }
-  c->slots.clear();
-  if (c->plain_done) (void)hipEventDestroy(c->plain_done);
-  FreeDev(c->d_nodes); FreeDev(c->d_tris); FreeDev(c->d_mats); FreeDev(c->d_bvhs); FreeDev(c->d_lights);
-  FreeDev(c->d_tex); FreeDev(c->d_tex_info); FreeDev(c->d_tri_uv);
-  FreeDev(c->d_noise_xy); FreeDev(c->d_noise_u); FreeDev(c->d_stats); FreeDev(c->d_nan); FreeDev(c->d_lbuf); FreeDev(c->d_gstack);
-  FreeDev(c->d_batch_ctr); FreeDev(c->d_tile_cost); FreeDev(c->d_tile_order); FreeDev(c->d_row_map); FreeDev(c->d_span);
-  FreeDev(c->d_wf_rec); FreeDev(c->d_wf_res); FreeDev(c->d_wf_state); FreeDev(c->d_wf_rayq); FreeDev(c->d_wf_hitq);
-  FreeDev(c->d_wf_ctl); FreeDev(c->d_wf_items);
-  FreeDev(c->d_nodes_t); FreeDev(c->d_troot); FreeDev(c->d_tl_ray); FreeDev(c->d_tl_stk); FreeDev(c->d_tl_slist);
-  FreeDev(c->d_tl_skey); FreeDev(c->d_tl_blist); FreeDev(c->d_tl_rlist); FreeDev(c->d_tl_count); FreeDev(c->d_tl_fill);
-  if (c->h_wf_poll) (void)hipHostFree(c->h_wf_poll);
-  for (hipEvent_t e : c->wf_poll_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  if (!c->images_external) { FreeDev(c->d_accum); FreeDev(c->d_out); }
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return SRT_OK;
-}
-
-void* srt_stream(srt_context* c) { return c ? static_cast<void*>(c->stream) : nullptr; }
-
-int srt_set_bool(srt_context* c, const char* name, int v) {
-  if (!c || !name) return SRT_ERR_INVALID;
-  const std::string n(name);
-  if (n == "resetAccumBuffer") c->reset = v ? 1 : 0;
-  else if (n == "showModel") c->show_model = v ? 1 : 0;
-  else return SRT_ERR_NOT_FOUND;
-  return SRT_OK;
-}
-
-int srt_set_int(srt_context* c, const char* name, int v) {
-  if (!c || !name) return SRT_ERR_INVALID;
-  const std::string n(name);
-  if (n == "Width") c->W = v;
-  else if (n == "Height") c->H = v;
-  else if (n == "accumFrames") c->accum_frames = v;
-  else if (n == "lightCount") c->light_count = v;
-  else if (n == "maxDepth") c->max_depth = v;
-  else if (n == "resetAccumBuffer" || n == "showModel") return srt_set_bool(c, name, v);
-  else if (n == "bvh_count") c->bvh_count = (uint32_t)v;
-  else return SRT_ERR_NOT_FOUND;
-  return SRT_OK;
-}
-
-int srt_set_uint(srt_context* c, const char* name, uint32_t v) {
-  if (!c || !name) return SRT_ERR_INVALID;
-  if (std::string(name) == "bvh_count") {
-    c->bvh_count = v;
-    return SRT_OK;
-  }
-  return srt_set_int(c, name, (int)v);
-}
-
-int srt_set_float(srt_context* c, const char* name, float v) {
-  if (!c || !name) return SRT_ERR_INVALID;
-  (void)v;
-  return SRT_ERR_NOT_FOUND;  // the kernel declares no float uniforms
-}
-
-int srt_set_vec3(srt_context* c, const char* name, float x, float y, float z) {
-  if (!c || !name) return SRT_ERR_INVALID;
-  const std::string n(name);
-  float* dst = nullptr;
-  if (n == "cameraOrigin") dst = c->cam_origin;
-  else if (n == "cameraDirection") dst = c->cam_dir;
-  else if (n == "cameraUp") dst = c->cam_up;
-  else if (n == "cameraRight") dst = c->cam_right;
-  else return SRT_ERR_NOT_FOUND;
-  dst[0] = x; dst[1] = y; dst[2] = z;
-  return SRT_OK;
-}
-
-int srt_set_tiling(srt_context* c, int rank, int nranks, int band_rows) {
-  if (!c || nranks < 1 || rank < 0 || rank >= nranks || band_rows < 1) return SRT_ERR_INVALID;
-  c->rank = rank;
-  c->nranks = nranks;
-  c->band_rows = band_rows;
-  return SRT_OK;
-}
-
-int srt_local_rows(srt_context* c) { return c ? LocalRows(c, c->H) : -1; }
-
-int srt_device(srt_context* c) { return c ? c->device : -1; }
-
-int srt_get_int(srt_context* c, const char* name, int* v) {
-  if (!c || !name || !v) return SRT_ERR_INVALID;
-  const std::string n(name);
-  if (n == "Width") *v = c->W;
-  else if (n == "Height") *v = c->H;
-  else if (n == "accumFrames") *v = c->accum_frames;
-  else if (n == "lightCount") *v = c->light_count;
-  else if (n == "maxDepth") *v = c->max_depth;
-  else if (n == "bvh_count") *v = (int)c->bvh_count;
-  else if (n == "resetAccumBuffer") *v = c->reset;
-  else if (n == "showModel") *v = c->show_model;
-  else if (n == "scene.fused") *v = c->fused ? 1 : 0;
-  else if (n == "scene.top_depth") *v = c->top_depth;  // levels in the fused instance's LDS copy (0: none)
-  else if (n == "scene.top_f4") *v = c->top_f4;
-  else if (n == "launch.top_f4") *v = c->launch_top_f4;
-  else if (n == "scene.global_waves") *v = c->global_waves;
-  else if (n == "scene.wavefront") *v = c->wavefront >= 0 ? c->wavefront : (c->wf_scene ? 1 : 0);
-  else if (n == "scene.wf_waves") *v = c->wf_waves;
-  else if (n == "scene.treelets") *v = (int)c->n_treelets;
-  else if (n == "scene.tri_slots") *v = (int)c->n_tris;  // device triangle records (LayoutTris gaps included)
-  else if (n == "launch.chunks") *v = c->ev_used / 2;   // sample launches of the last render or dispatch
-  else if (n == "launch.overlap") *v = c->launch_overlap ? 1 : 0;  // what the last render's launches did
-  else if (n == "launch.blocks_per_cu") *v = c->launch_per_cu;      // resident blocks per CU of the last sample launch
-  else if (n == "launch.block") *v = c->launch_block;               // its lanes per block
-  else if (n == "launch.mats_lds") *v = c->launch_mats_lds;          // 1: it read the material records from LDS
-  else return SRT_ERR_NOT_FOUND;
-  return SRT_OK;
-}
 
 int srt_dispatch(srt_context* c, uint32_t gx, uint32_t gy) {
   if (!c) return SRT_ERR_INVALID;
@@ -1713,125 +997,6 @@ extern "C" int srt_debug_wave_trace(srt_context* c, unsigned long long* out, int
   return n;
 }
 #endif
-
-// Kernel time of sample launches from their span records (first wave's start, last wave's end; 100 MHz
-// ticks): the time during which some sample launch of the context runs, i.e. the union of the spans.
-// Launches in series add their spans.  Overlapped pipeline slots dispatch a launch while its
-// predecessor still runs -- it starts in the CUs the drain frees, or, when the host has enqueued several
-// ahead, the hardware may run two slots' launches side by side or the later one first -- so a span then
-// includes the wait for CUs another launch holds, and only the union is the launches' device time.
-namespace {
-bool SpanRecord(const srt_context* c, const unsigned long long* ring, unsigned long long q, unsigned long long* t0,
-                unsigned long long* t1) {
-  if (q >= c->span_seq || q + srt_context::kSpanCap < c->span_seq) return false;  // not written, or overwritten
-  const unsigned long long* sp = ring + 2 * (q % srt_context::kSpanCap);
-  if (sp[1] < sp[0]) return false;
-  *t0 = sp[0];
-  *t1 = sp[1];
-  return true;
-}
-// Union of the spans of records [from, to) in ms, counting only time after `after` (a tick); *last_end
-// receives the latest end seen (or `after`).
-double SpanUnionMs(const srt_context* c, const unsigned long long* ring, unsigned long long from,
-                   unsigned long long to, unsigned long long after, unsigned long long* last_end) {
-  std::vector<std::pair<unsigned long long, unsigned long long>> iv;
-  for (unsigned long long q = from; q < to; ++q) {
-    unsigned long long t0, t1;
-    if (SpanRecord(c, ring, q, &t0, &t1)) iv.push_back({std::max(t0, after), std::max(t1, after)});
-  }
-  std::sort(iv.begin(), iv.end());
-  unsigned long long covered = 0, reach = after;
-  for (const auto& [a, b] : iv) {
-    const unsigned long long lo = std::max(a, reach);
-    if (b > lo) covered += b - lo;
-    reach = std::max(reach, b);
-  }
-  if (last_end) *last_end = reach;
-  return (double)covered * 1e-5;
-}
-}  // namespace
-
-int srt_last_kernel_ms(srt_context* c, float* ms) {
-  if (!c || !ms) return SRT_ERR_INVALID;
-  *ms = 0.0f;
-  std::vector<unsigned long long> ring;
-  unsigned long long lo = ~0ull, hi = 0;  // the render's span records (its chunks' launches are consecutive)
-  for (int i = 0; i + 1 < c->ev_used; i += 2) {
-    HIP_OK(hipEventSynchronize(c->ev[i + 1]));
-    const size_t chunk = (size_t)(i / 2);
-    const long long rec = chunk < c->chunk_span.size() ? c->chunk_span[chunk] : -1;
-    if (rec >= 0 && (unsigned long long)rec + srt_context::kSpanCap >= c->span_seq) {  // the launch's own span
-      lo = std::min(lo, (unsigned long long)rec);
-      hi = std::max(hi, (unsigned long long)rec + 1);
-      continue;
-    }
-    float t = 0.0f;  // pool and wavefront launches: the HIP events around them
-    HIP_OK(hipEventElapsedTime(&t, c->ev[i], c->ev[i + 1]));
-    *ms += t;
-  }
-  if (lo < hi) {
-    ring.resize(2 * srt_context::kSpanCap);
-    HIP_OK(hipMemcpy(ring.data(), c->d_span, sizeof(unsigned long long) * ring.size(), hipMemcpyDeviceToHost));
-    *ms += (float)SpanUnionMs(c, ring.data(), lo, hi, 0ull, nullptr);
-  }
-  return SRT_OK;
-}
-
-int srt_kernel_time(srt_context* c, double* total_ms, int* launches) {
-  if (!c || !total_ms || !launches) return SRT_ERR_INVALID;
-  *total_ms = 0.0;
-  *launches = 0;
-  HIP_OK(hipStreamSynchronize(c->stream));
-  if (int rq = Quiesce(c)) return rq;
-  const unsigned long long from = c->span_read;
-  c->span_read = c->span_seq;
-  if (c->span_seq - from > (unsigned long long)srt_context::kSpanCap) {  // records were overwritten unread
-    srt::SetError("srt_kernel_time: more than 4096 sample launches since the last call (span records lost)");
-    return SRT_ERR_LIMIT;
-  }
-  if (c->span_seq > from) {
-    std::vector<unsigned long long> ring(2 * srt_context::kSpanCap);
-    HIP_OK(hipMemcpy(ring.data(), c->d_span, sizeof(unsigned long long) * ring.size(), hipMemcpyDeviceToHost));
-    // (time before the end of the launches read by the previous call was counted there)
-    *total_ms = SpanUnionMs(c, ring.data(), from, c->span_seq, c->span_done, &c->span_done);
-    *launches = (int)(c->span_seq - from);
-  }
-  return SRT_OK;
-}
-
-int srt_get_stats(srt_context* c, srt_stats* out) {
-  if (!c || !out) return SRT_ERR_INVALID;
-  *out = c->stats;
-  return SRT_OK;
-}
-
-int srt_ray_kinds(srt_context* c, uint64_t kinds[3]) {
-  if (!c || !kinds) return SRT_ERR_INVALID;
-  kinds[0] = c->stats.samples;  // one camera ray per path sample
-  kinds[1] = c->shadow_rays;
-  kinds[2] = c->stats.rays - c->stats.samples - c->shadow_rays;
-  return SRT_OK;
-}
-
-int srt_reset_stats(srt_context* c) {
-  if (!c) return SRT_ERR_INVALID;
-  c->stats = srt_stats{};
-  c->shadow_rays = 0;
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemsetAsync(c->d_nan, 0, sizeof(unsigned long long), c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return SRT_OK;
-}
-
-int srt_nan_samples(srt_context* c, uint64_t* out) {
-  if (!c || !out) return SRT_ERR_INVALID;
-  unsigned long long v = 0;
-  HIP_OK(hipSetDevice(c->device));
-  HIP_OK(hipMemcpyAsync(&v, c->d_nan, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  *out = v;
-  return SRT_OK;
-}
 
 int srt_upload_scene(srt_context* c, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes,
                      uint32_t n_nodes, const srt_material_obj* mats, const float* tex_albedo, uint32_t n_mats,
@@ -2190,203 +1355,6 @@ int srt_update_model_matrix(srt_context* c, uint32_t index, const float frame[16
   std::memcpy(c->h_bvhs[index].frame, frame, sizeof(float) * 16);
   c->bvhs_dirty = true;
   return SRT_OK;  // pushed to the device at the next launch (EnsureBvhs)
-}
-
-int srt_set_lights(srt_context* c, const srt_light* lights, uint32_t n) {
-  if (!c || (n && !lights)) return SRT_ERR_INVALID;
-  c->h_lights.assign(lights, lights + n);
-  c->lights_dirty = true;
-  return SRT_OK;
-}
-
-int srt_set_noise(srt_context* c, const float* noise_rgb, const float* noise_u_rgb, size_t texels) {
-  if (!c || !noise_rgb || !noise_u_rgb || texels == 0) return SRT_ERR_INVALID;
-  HIP_OK(hipSetDevice(c->device));
-  if (int rq = Quiesce(c)) return rq;
-  std::vector<float2> xy(texels);
-  std::vector<float> u(texels);
-  for (size_t i = 0; i < texels; ++i) {
-    xy[i] = make_float2(noise_rgb[3 * i], noise_rgb[3 * i + 1]);
-    u[i] = noise_u_rgb[3 * i];
-  }
-  if (texels != c->noise_texels) {
-    FreeDev(c->d_noise_xy); FreeDev(c->d_noise_u);
-    c->d_noise_xy = nullptr; c->d_noise_u = nullptr; c->noise_texels = 0;
-    HIP_OK(hipMalloc(&c->d_noise_xy, texels * sizeof(float2)));
-    HIP_OK(hipMalloc(&c->d_noise_u, texels * sizeof(float)));
-  }
-  HIP_OK(hipMemcpyAsync(c->d_noise_xy, xy.data(), texels * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipMemcpyAsync(c->d_noise_u, u.data(), texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  c->noise_texels = texels;
-  return SRT_OK;
-}
-
-int srt_alloc_images(srt_context* c) {
-  if (!c || c->W <= 0 || c->H <= 0) return SRT_ERR_STATE;
-  HIP_OK(hipSetDevice(c->device));
-  const int rows = LocalRows(c, c->H);
-  const size_t px = (size_t)c->W * (size_t)std::max(rows, 1);
-  if (!c->images_external) { FreeDev(c->d_accum); FreeDev(c->d_out); }
-  c->images_external = false;
-  c->d_accum = nullptr; c->d_out = nullptr;
-  HIP_OK(hipMalloc(&c->d_accum, px * sizeof(float4)));
-  HIP_OK(hipMalloc(&c->d_out, px * sizeof(uint32_t)));
-  HIP_OK(hipMemsetAsync(c->d_accum, 0, px * sizeof(float4), c->stream));
-  HIP_OK(hipMemsetAsync(c->d_out, 0, px * sizeof(uint32_t), c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  c->img_w = c->W;
-  c->img_rows = rows;
-  return SRT_OK;
-}
-
-int srt_read_accum(srt_context* c, float* host, size_t bytes) {
-  if (!c || !host || !c->d_accum) return SRT_ERR_INVALID;
-  const size_t need = (size_t)c->img_w * c->img_rows * sizeof(float4);
-  if (bytes < need) return SRT_ERR_INVALID;
-  HIP_OK(hipMemcpyAsync(host, c->d_accum, need, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return SRT_OK;
-}
-
-int srt_write_accum(srt_context* c, const float* host, size_t bytes) {
-  if (!c || !host || !c->d_accum) return SRT_ERR_INVALID;
-  const size_t need = (size_t)c->img_w * c->img_rows * sizeof(float4);
-  if (bytes < need) return SRT_ERR_INVALID;
-  HIP_OK(hipMemcpyAsync(c->d_accum, host, need, hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return SRT_OK;
-}
-
-namespace {
-constexpr char kCkptMagic[8] = {'S', 'R', 'T', 'C', 'K', 'P', 'T', '1'};
-struct CkptHeader {
-  char magic[8];
-  int32_t version, width, local_rows, rank, nranks, band_rows, accum_frames, pad;
-  float cam[12];  // cameraOrigin, cameraDirection, cameraUp, cameraRight
-  uint64_t payload_bytes;
-  uint32_t payload_crc, header_crc;
-};
-uint32_t Crc32(const void* p, size_t n) {
-  return (uint32_t)crc32(0L, static_cast<const Bytef*>(p), (uInt)n);
-}
-}  // namespace
-
-int srt_checkpoint_save(srt_context* c, const char* path) {
-  if (!c || !path || !c->d_accum || c->img_w <= 0 || c->img_rows <= 0) return SRT_ERR_INVALID;
-  std::vector<float> acc((size_t)c->img_w * c->img_rows * 4);
-  int rc = srt_read_accum(c, acc.data(), acc.size() * sizeof(float));
-  if (rc) return rc;
-  CkptHeader h{};
-  std::memcpy(h.magic, kCkptMagic, 8);
-  h.version = 1;
-  h.width = c->img_w;
-  h.local_rows = c->img_rows;
-  h.rank = c->rank;
-  h.nranks = c->nranks;
-  h.band_rows = c->band_rows;
-  h.accum_frames = c->accum_frames;
-  const float* cam[4] = {c->cam_origin, c->cam_dir, c->cam_up, c->cam_right};
-  for (int i = 0; i < 4; ++i) std::memcpy(h.cam + 3 * i, cam[i], 3 * sizeof(float));
-  h.payload_bytes = acc.size() * sizeof(float);
-  h.payload_crc = Crc32(acc.data(), h.payload_bytes);
-  h.header_crc = Crc32(&h, offsetof(CkptHeader, header_crc));
-  const std::string tmp = std::string(path) + ".tmp";
-  FILE* f = std::fopen(tmp.c_str(), "wb");
-  if (!f) {
-    srt::SetError(std::string("srt_checkpoint_save: cannot open ") + tmp);
-    return SRT_ERR_IO;
-  }
-  const bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(acc.data(), 1, h.payload_bytes, f) == h.payload_bytes;
-  if (std::fclose(f) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) {  // the old file survives a failed save
-    std::remove(tmp.c_str());
-    srt::SetError(std::string("srt_checkpoint_save: cannot write ") + path);
-    return SRT_ERR_IO;
-  }
-  return SRT_OK;
-}
-
-int srt_checkpoint_load(srt_context* c, const char* path, int32_t* accum_frames) {
-  if (!c || !path || !c->d_accum) return SRT_ERR_INVALID;
-  FILE* f = std::fopen(path, "rb");
-  if (!f) {
-    srt::SetError(std::string("srt_checkpoint_load: cannot open ") + path);
-    return SRT_ERR_IO;
-  }
-  CkptHeader h{};
-  std::vector<float> acc;
-  bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, kCkptMagic, 8) == 0 && h.version == 1 &&
-            h.header_crc == Crc32(&h, offsetof(CkptHeader, header_crc));
-  if (ok && (h.width != c->img_w || h.local_rows != c->img_rows || h.rank != c->rank || h.nranks != c->nranks ||
-             h.band_rows != c->band_rows || h.payload_bytes != (uint64_t)c->img_w * c->img_rows * 16)) {
-    std::fclose(f);
-    srt::SetError("srt_checkpoint_load: the checkpoint's frame or tiling differs from the context's");
-    return SRT_ERR_INVALID;
-  }
-  if (ok) {
-    acc.resize(h.payload_bytes / sizeof(float));
-    ok = std::fread(acc.data(), 1, h.payload_bytes, f) == h.payload_bytes &&
-         Crc32(acc.data(), h.payload_bytes) == h.payload_crc;
-  }
-  std::fclose(f);
-  if (!ok) {
-    srt::SetError(std::string("srt_checkpoint_load: not a valid checkpoint (truncated or corrupt): ") + path);
-    return SRT_ERR_IO;
-  }
-  const int rc = srt_write_accum(c, acc.data(), h.payload_bytes);
-  if (rc) return rc;
-  c->accum_frames = h.accum_frames;
-  float* cam[4] = {c->cam_origin, c->cam_dir, c->cam_up, c->cam_right};
-  for (int i = 0; i < 4; ++i) std::memcpy(cam[i], h.cam + 3 * i, 3 * sizeof(float));
-  if (accum_frames) *accum_frames = h.accum_frames;
-  return SRT_OK;
-}
-
-int srt_read_output(srt_context* c, uint8_t* host, size_t bytes) {
-  if (!c || !host || !c->d_out) return SRT_ERR_INVALID;
-  const size_t need = (size_t)c->img_w * c->img_rows * sizeof(uint32_t);
-  if (bytes < need) return SRT_ERR_INVALID;
-  HIP_OK(hipMemcpyAsync(host, c->d_out, need, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return SRT_OK;
-}
-
-int srt_write_output(srt_context* c, const char* path, int flip_y) {
-  if (!c || !path || !c->d_out || c->img_w <= 0 || c->img_rows <= 0) return SRT_ERR_INVALID;
-  std::vector<uint8_t> px((size_t)c->img_w * c->img_rows * 4);
-  const int rc = srt_read_output(c, px.data(), px.size());
-  if (rc) return rc;
-  return srt_image_write(path, px.data(), c->img_w, c->img_rows, flip_y);
-}
-
-int srt_set_image_buffers(srt_context* c, void* accum_dev, void* out_dev) {
-  if (!c || !accum_dev || !out_dev || c->W <= 0 || c->H <= 0) return SRT_ERR_INVALID;
-  if (!c->images_external) { FreeDev(c->d_accum); FreeDev(c->d_out); }
-  c->d_accum = static_cast<float4*>(accum_dev);
-  c->d_out = static_cast<uint32_t*>(out_dev);
-  c->images_external = true;
-  c->img_w = c->W;
-  c->img_rows = LocalRows(c, c->H);
-  return SRT_OK;
-}
-
-int srt_assemble_bands(srt_context* c, const void* gathered, int nranks, int rows_pad, int band_rows, int frames,
-                       void* accum_full, void* out_full) {
-  return c ? srt::AssembleBandsOn(c, c->stream, gathered, nranks, rows_pad, band_rows, frames, accum_full, out_full)
-           : SRT_ERR_INVALID;
-}
-
-int srt_assemble_output_bands(srt_context* c, const void* gathered_rgba8, int nranks, int rows_pad, int band_rows,
-                              void* out_full) {
-  return c ? srt::AssembleOutputOn(c, c->stream, gathered_rgba8, nranks, rows_pad, band_rows, c->W, c->H, out_full)
-           : SRT_ERR_INVALID;
-}
-
-int srt_image_pointers(srt_context* c, void** accum_dev, void** out_dev) {
-  if (!c) return SRT_ERR_INVALID;
-  if (accum_dev) *accum_dev = c->d_accum;
-  if (out_dev) *out_dev = c->d_out;
-  return SRT_OK;
 }
 
 int srt_trace_closest(srt_context* c, const srt_ray* rays, uint32_t n, uint32_t* hits, float* t_out) {

@@ -41,7 +41,7 @@ enum { PC_HEAD = 0, PC_TAIL = 3, PC_AVAIL = 6, PC_LIVE = 9, PC_EXH = 10, PC_ERR 
 constexpr uint32_t kFlagShadow = 1u << 8, kFlagTerm = 1u << 9;
 
 // Diagnostic build (-DSRT_POOL_STATS): per-wave event counts and shader-clock cycles, summed into
-// stats[ST_DBG_SUB + k] (tools/pool_check.py prints them).
+// stats[ST_DBG_SUB + k] (tools/probes/pool_check.py prints them).
 enum { PD_T_OUTER = 0, PD_T_INNER, PD_T_ACTIVE, PD_T_IDLE, PD_T_SWAPPED, PD_T_HITS, PD_T_CYC_SWAP, PD_T_CYC_TRAV,
        PD_T_CYC_IDLE, PD_S_PASS, PD_S_POPPED, PD_S_DONE, PD_T_SPARE, PD_T_NEW, PD_S_IDLE, PD_S_CYC_BUSY, PD_S_CYC_IDLE,
        PD_T_WAIT, PD_T_C_RET, PD_T_C_POP, PD_T_C_SPARE, PD_T_C_REFILL, PD_T_C_START, PD_N };

@@ -129,12 +129,25 @@ bool ProgressiveFrame(CameraState* cam, const Vec3& move, float rot_x, float rot
 
 void SetError(const std::string& msg);
 
+// Constants of the device code that host files need too (device_common.hpp includes this header).
+// Indices into the launch statistics (KParams::stats):
+enum { ST_RAYS = 0, ST_NODES, ST_TRIS, ST_RNGU, ST_RNGSQ, ST_LIGHTS, ST_MATS, ST_SAMPLES, ST_OVERFLOW, ST_MAXSTACK,
+       ST_BOUNCECAP,  // paths cut at the bounce cap (KParams::bounce_cap)
+       ST_SHADOW,     // shadow rays among ST_RAYS (CheckLightOccluded, raytrace_compute.glsl:167-176)
+       ST_N, ST_CYC_REFILL = ST_N, ST_CYC_TRAV, ST_CYC_SHADE, ST_CYC_ITERS,
+       // lane occupancy of the traversal loop (summed popcounts per iteration) and of shading
+       ST_DBG_TITERS, ST_DBG_WORK, ST_DBG_TRAV, ST_DBG_LEAF, ST_DBG_INT, ST_DBG_SHADE,
+       // per traversal sub-step k < 16: lanes taking it (summed), waves executing it, lanes popping after it
+       ST_DBG_SUB, ST_POOLERR = ST_DBG_SUB + 48,  // pool_kernel's watchdog fired (pool.hpp)
+       ST_TOTAL };
+constexpr int kTopStack = 16;  // top-level stack entries saved per suspended ray (treelet depth < this; wavefront.hpp)
+
 // pathtrace.hip: the multi-GPU root's assembly on a given HIP stream (group.cpp's gather stream)
 int AssembleBandsOn(srt_context* c, void* stream, const void* gathered, int nranks, int rows_pad, int band_rows,
                     int frames, void* accum_full, void* out_full);
 int AssembleOutputOn(srt_context* c, void* stream, const void* gathered_rgba8, int nranks, int rows_pad,
                      int band_rows, int ext_w, int ext_h, void* out_full);
-// pathtrace.hip: a context leaves a device group without allocating: rank 0 of 1, no images (a
+// context.cpp: a context leaves a device group without allocating: rank 0 of 1, no images (a
 // dispatch returns SRT_ERR_STATE until it is given images again)
 int DetachImages(srt_context* c);
 

@@ -380,7 +380,7 @@ static_assert((kShortStack & (kShortStack - 1)) == 0, "kShortStack must be a pow
 constexpr int kTriPad = 3;                // zero records past the triangle array (>= kLeafTris - 1)
 constexpr uint32_t kNodePad = 2;          // zero node records past the array: the speculative next-pair read
 // Internal steps expand the right child in the same step when its child pair
-// is the next pair of the array (trav_internal; pathtrace.hip LayoutNodes).
+// is the next pair of the array (trav_internal; scene_layout.cpp LayoutNodes).
 #ifndef SRT_SPINE
 #define SRT_SPINE 1
 #endif

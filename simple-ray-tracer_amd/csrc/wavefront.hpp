@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256, GW) void wf_trace_kernel(KParams kp, WfParams 
 // once for all the rays that visit it in the iteration; the next iteration's top kernel resumes the ray
 // with its saved top-level stack (the next pop).  Each ray's steps are the reference's, in order.
 // ---------------------------------------------------------------------------
-constexpr int kTopStack = 16;  // top-level stack entries saved per suspended ray (treelet depth < this)
+// (kTopStack, the top-level stack entries saved per suspended ray: srt_internal.hpp)
 
 // a suspended ray: (o, dist) (d, hit) (inv, root) (bvh, sp, 0, 0), o/d/inv in the current BVH's frame
 __device__ __forceinline__ float4* wf_tray(const WfParams& w, int k, uint32_t s) {

@@ -408,3 +408,21 @@ def test_obj_float_edge_lines(tmp_path):
     fmax = np.finfo(np.float32).max
     assert sc.mats[0]["diffuse"].tolist() == [0.5, 0.0, 0.0] and sc.mats[0]["Ks"][0] == fmax
     assert sc.mats[1]["diffuse"].tolist() == [0.0, 0.0, 0.0] and sc.mats[1]["Ns"] == -fmax
+
+
+def test_scene_layouts_under_sanitizers():
+    """tests/cpp/test_scene_layout.cpp with csrc/scene_layout.cpp (BVH validation, the device node and triangle
+    layouts, the span union) and the loader linked directly, AddressSanitizer + UBSan, as a stand-alone program
+    (host code only: no HIP, no device, nothing preloaded): hand-made trees, then Rubik's."""
+    from conftest import PKG, ROOT
+
+    out = ROOT / "tests" / "cpp" / "_build"
+    out.mkdir(exist_ok=True)
+    exe = out / "test_scene_layout_san"
+    subprocess.run(["g++", "-std=c++17", "-O0", "-Wall", "-fsanitize=address,undefined",  # (-O0: half the compile time)
+                    "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                    str(ROOT / "tests" / "cpp" / "test_scene_layout.cpp"), str(PKG / "csrc" / "scene_layout.cpp"),
+                    str(PKG / "csrc" / "scene.cpp"), "-o", str(exe), "-lz", "-pthread"], check=True)
+    r = subprocess.run([str(exe), str(RUBIK)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "Rubik: 1188 triangles, 427 nodes, depth 9" in r.stdout and "scene layout checks OK" in r.stdout
