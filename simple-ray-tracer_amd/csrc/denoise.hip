@@ -1,0 +1,226 @@
+// denoise.hip -- the denoiser of include/srt_denoise.h: the object, its buffers and the launches of
+// denoise.hpp's kernels in denoise_host.hpp's schedule.  A translation unit of its own, as query.hip is:
+// pathtrace.hip and its headers (the device code srt_code_hash identifies) are only read.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../include/srt_denoise.h"
+#include "denoise.hpp"
+#include "denoise_host.hpp"
+
+#define DHIP_OK(expr)                                                         \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                   \
+      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
+      return SRT_ERR_HIP;                                                     \
+    }                                                                         \
+  } while (0)
+
+struct srt_denoiser {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int width = 0, height = 0;
+  srt::denoise::Sizes sizes;
+  float4* d_color[2] = {nullptr, nullptr};  // ping-pong colour | id
+  float4* d_guide = nullptr;                // normal | t
+  srt_denoise_params params;
+  int tile_max_step = 0;
+  int last_launches = 0;
+};
+
+namespace {
+
+using srt::denoise::DParams;
+using srt::denoise::kBlock;
+using srt::denoise::Pass;
+
+void FreeAll(srt_denoiser* dn) {
+  for (float4* p : dn->d_color)
+    if (p) (void)hipFree(p);
+  if (dn->d_guide) (void)hipFree(dn->d_guide);
+  if (dn->own_stream && dn->stream) (void)hipStreamDestroy(dn->stream);
+}
+
+int Allocate(srt_denoiser* dn) {
+  DHIP_OK(hipSetDevice(dn->device));
+  if (!dn->stream) {
+    DHIP_OK(hipStreamCreateWithFlags(&dn->stream, hipStreamNonBlocking));
+    dn->own_stream = true;
+  }
+  DHIP_OK(hipMalloc(&dn->d_color[0], dn->sizes.color_bytes));
+  DHIP_OK(hipMalloc(&dn->d_color[1], dn->sizes.color_bytes));
+  DHIP_OK(hipMalloc(&dn->d_guide, dn->sizes.guide_bytes));
+  const size_t lds = dn->tile_max_step ? srt::denoise::TileLdsBytes(dn->tile_max_step) : 0;
+  if (lds > 48 * 1024) {
+    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_denoise_abi_version(void) { return SRT_DENOISE_ABI_VERSION; }
+
+int srt_denoise_create(int device, void* stream, int width, int height, srt_denoiser** out) {
+  if (!out) return SRT_ERR_INVALID;
+  *out = nullptr;
+  srt::denoise::Sizes sizes;
+  if (int rc = srt::denoise::PlanBuffers(width, height, &sizes)) {  // before any device is touched
+    srt::SetError(rc == SRT_ERR_LIMIT ? "srt_denoise_create: image past 65535 in a dimension or 2^28 pixels"
+                                      : "srt_denoise_create: width and height must be at least 1");
+    return rc;
+  }
+  srt_denoiser* dn = new srt_denoiser();
+  dn->device = device;
+  dn->stream = static_cast<hipStream_t>(stream);
+  dn->width = width;
+  dn->height = height;
+  dn->sizes = sizes;
+  dn->params = srt::denoise::DefaultParams();
+  dn->tile_max_step = srt::denoise::TileMaxStep(std::getenv("SRT_DENOISE_TILE"));
+  if (int rc = Allocate(dn)) {
+    FreeAll(dn);
+    delete dn;
+    return rc;
+  }
+  *out = dn;
+  return SRT_OK;
+}
+
+int srt_denoise_destroy(srt_denoiser* dn) {
+  if (!dn) return SRT_ERR_INVALID;
+  (void)hipSetDevice(dn->device);
+  if (dn->stream) (void)hipStreamSynchronize(dn->stream);
+  FreeAll(dn);
+  delete dn;
+  return SRT_OK;
+}
+
+void* srt_denoise_stream(srt_denoiser* dn) { return dn ? dn->stream : nullptr; }
+
+int srt_denoise_get_int(srt_denoiser* dn, const char* name, int* v) {
+  if (!dn || !name || !v) return SRT_ERR_INVALID;
+  const std::string n(name);
+  if (n == "passes") *v = (int)dn->params.passes;
+  else if (n == "normal_squarings") *v = (int)dn->params.normal_squarings;
+  else if (n == "width") *v = dn->width;
+  else if (n == "height") *v = dn->height;
+  else if (n == "scratch.bytes") *v = (int)(dn->sizes.scratch_bytes < 0x7FFFFFFFu ? dn->sizes.scratch_bytes : 0x7FFFFFFFu);
+  else if (n == "tile.lds_bytes") *v = dn->tile_max_step ? (int)srt::denoise::TileLdsBytes(dn->tile_max_step) : 0;
+  else if (n == "tile.max_step") *v = dn->tile_max_step;
+  else if (n == "tile.width") *v = srt::denoise::kTileW;
+  else if (n == "tile.height") *v = srt::denoise::kTileH;
+  else if (n == "launches") *v = dn->last_launches;
+  else return SRT_ERR_NOT_FOUND;
+  return SRT_OK;
+}
+
+int srt_denoise_get_params(srt_denoiser* dn, srt_denoise_params* p) {
+  if (!dn || !p) return SRT_ERR_INVALID;
+  *p = dn->params;
+  return SRT_OK;
+}
+
+int srt_denoise_set_params(srt_denoiser* dn, const srt_denoise_params* p) {
+  if (!dn) return SRT_ERR_INVALID;
+  if (int rc = srt::denoise::ValidateParams(p)) {
+    srt::SetError("srt_denoise_set_params: passes and normal_squarings 0..8, sigmas finite and > 0");
+    return rc;
+  }
+  dn->params = *p;
+  return SRT_OK;
+}
+
+int srt_denoise_primary_rays(srt_denoiser* dn, const float origin[3], const float front[3], const float right[3],
+                             const float up[3], srt_ray* rays_dev) {
+  if (!dn || !origin || !front || !right || !up || !rays_dev || ((uintptr_t)rays_dev & 15u)) return SRT_ERR_INVALID;
+  srt::denoise::Basis b;
+  srt::denoise::PrimaryBasis(origin, front, right, up, dn->width, dn->height, &b);
+  srt::denoise::RayParams rp;
+  rp.rays = reinterpret_cast<float4*>(rays_dev);
+  rp.W = dn->width;
+  rp.H = dn->height;
+  std::memcpy(rp.o, b.o, sizeof rp.o);
+  std::memcpy(rp.p00, b.p00, sizeof rp.p00);
+  std::memcpy(rp.du, b.du, sizeof rp.du);
+  std::memcpy(rp.dv, b.dv, sizeof rp.dv);
+  DHIP_OK(hipSetDevice(dn->device));
+  const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(srt::denoise::primary_rays_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream, rp);
+  DHIP_OK(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_denoise_run(srt_denoiser* dn, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                    void* out_rgba32f_dev, void* out_rgba8_dev) {
+  if (!dn || !accum_rgba32f_dev || frames < 1 || (!out_rgba32f_dev && !out_rgba8_dev)) return SRT_ERR_INVALID;
+  if (dn->params.passes > 0 && !guide_dev) {
+    srt::SetError("srt_denoise_run: a guide is needed when passes > 0");
+    return SRT_ERR_INVALID;
+  }
+  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u) ||
+      ((uintptr_t)out_rgba8_dev & 3u)) {
+    srt::SetError("srt_denoise_run: accum, guide and out_rgba32f must be 16-byte aligned, out_rgba8 4-byte");
+    return SRT_ERR_INVALID;
+  }
+  DHIP_OK(hipSetDevice(dn->device));
+  DParams dp;
+  std::memset(&dp, 0, sizeof dp);
+  dp.hits = reinterpret_cast<const uint4*>(guide_dev);
+  dp.guide = dn->d_guide;
+  dp.W = dn->width;
+  dp.H = dn->height;
+  dp.nsq = (int)dn->params.normal_squarings;
+  dp.frames = (float)frames;
+  dp.sigma_d = dn->params.sigma_depth;
+  float4* const out32 = static_cast<float4*>(out_rgba32f_dev);
+  uint32_t* const out8 = static_cast<uint32_t*>(out_rgba8_dev);
+  Pass sched[SRT_DENOISE_MAX_PASSES];
+  const int n = srt::denoise::BuildSchedule(dn->params, dn->tile_max_step, dn->width, dn->height, sched);
+  if (n == 0) {
+    dp.src = static_cast<const float4*>(accum_rgba32f_dev);
+    dp.out32 = out32;
+    dp.out8 = out8;
+    const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(srt::denoise::denoise_resolve_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream, dp);
+    DHIP_OK(hipGetLastError());
+    dn->last_launches = 1;
+    return SRT_OK;
+  }
+  for (int i = 0; i < n; ++i) {
+    const Pass& ps = sched[i];
+    dp.src = ps.first ? static_cast<const float4*>(accum_rgba32f_dev) : dn->d_color[ps.src];
+    dp.dst = ps.last ? nullptr : dn->d_color[ps.dst];
+    dp.out32 = ps.last ? out32 : nullptr;
+    dp.out8 = ps.last ? out8 : nullptr;
+    dp.step = ps.step;
+    dp.sigma_c = ps.sigma_c;
+    const dim3 grid(ps.grid_x, ps.grid_y);
+    if (ps.tiled) {
+      if (ps.first)
+        hipLaunchKernelGGL(srt::denoise::denoise_tiled_kernel<true>, grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
+      else
+        hipLaunchKernelGGL(srt::denoise::denoise_tiled_kernel<false>, grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
+    } else {
+      if (ps.first)
+        hipLaunchKernelGGL(srt::denoise::denoise_direct_kernel<true>, grid, dim3(kBlock), 0, dn->stream, dp);
+      else
+        hipLaunchKernelGGL(srt::denoise::denoise_direct_kernel<false>, grid, dim3(kBlock), 0, dn->stream, dp);
+    }
+    DHIP_OK(hipGetLastError());
+  }
+  dn->last_launches = n;
+  return SRT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,219 @@
+// denoise.hpp -- the kernels of the edge-avoiding denoiser (include/srt_denoise.h; DESIGN.md section 5,
+// "Denoiser").
+//
+// One launch per pass.  A pixel is two float4: colour | id (id: the BVH record of its hit as bits, all ones
+// for a miss or a pixel outside the image) and normal | t, so a tap reads two 16-B words and its whole
+// rejection test is one compare of ids.  The first pass reads the accumulation sum and the 32-B srt_hit
+// records instead (mean and guide pack fused into its loads) and writes the packed guide for the later
+// passes; the last pass writes the outputs (sRGB8 encode fused into its store).
+//   denoise_tiled_kernel   small steps: a 32 x 8 tile and its halo of 2 * step pixels staged once in LDS
+//                          (linear 16-B loads and ds_write_b128; a wave's tap is 2 rows of 32 contiguous
+//                          float4 = every bank once per ds_read_b128 lane group, whatever the row stride)
+//   denoise_direct_kernel  large steps, where the halo outgrows the tile: taps are global dwordx4 loads, a
+//                          wave covering 64 contiguous pixels of one row
+// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division); the
+// sRGB8 encode is device_common.hpp's linearToSrgb / to_unorm8, read-only, as accumulate_kernel uses them.
+#pragma once
+
+#include "device_common.hpp"
+#include "denoise_host.hpp"
+
+namespace srt {
+namespace denoise {
+using namespace dev;
+
+constexpr uint32_t kMissId = 0xFFFFFFFFu;
+
+struct DParams {
+  const float4* src;   // colour | id of the previous pass; first pass: the accumulation image (sum | 1)
+  const uint4* hits;   // first pass: the srt_hit records, 2 uint4 each
+  float4* guide;       // normal | t: written by the first pass, read by the others
+  float4* dst;         // colour | id for the next pass (nullptr in the last pass)
+  float4* out32;       // last pass: (colour, 1) or nullptr
+  uint32_t* out8;      // last pass: sRGB8 or nullptr
+  int W, H, step;
+  int nsq;             // normal_squarings
+  float frames;        // first pass: float(frames)
+  float sigma_c, sigma_d;
+};
+
+struct Px {
+  float4 c;  // colour | id
+  float4 g;  // normal | t
+};
+
+__device__ __forceinline__ uint32_t px_id(const float4& c) { return __float_as_uint(c.w); }
+__device__ __forceinline__ bool finite1(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+__device__ __forceinline__ bool finite3(const float4& c) { return finite1(c.x) && finite1(c.y) && finite1(c.z); }
+
+// A whole 16-B word in one instruction (dwordx4 / ds_read_b128): the empty asm makes all four components
+// live, or the compiler splits the load at the component the id test reads first.
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld16(const float4* p) {
+  v4f v = *reinterpret_cast<const v4f*>(p);
+  asm("" : "+v"(v));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ uint4 ld16(const uint4* p) {
+  v4u v = *reinterpret_cast<const v4u*>(p);
+  asm("" : "+v"(v));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+template <bool FIRST>
+__device__ __forceinline__ Px load_px(const DParams& dp, int p) {
+  Px r;
+  if constexpr (FIRST) {
+    const float4 a = ld16(dp.src + p);
+    const uint4 h0 = ld16(dp.hits + 2 * (size_t)p), h1 = ld16(dp.hits + 2 * (size_t)p + 1);  // triangle t n.x n.y | n.z material bvh pad
+    const f3 o = mk(a.x, a.y, a.z) / dp.frames;
+    r.c = make_float4(o.x, o.y, o.z, __uint_as_float(h0.x == kMissId ? kMissId : h1.z));
+    r.g = make_float4(__uint_as_float(h0.z), __uint_as_float(h0.w), __uint_as_float(h1.x), __uint_as_float(h0.y));
+  } else {
+    r.c = ld16(dp.src + p);
+    r.g = ld16(dp.guide + p);
+  }
+  return r;
+}
+
+// One tap of a pixel whose own id is a hit's.  `k` is the B3-spline weight h[|dx|] * h[|dy|].
+__device__ __forceinline__ void tap(const DParams& dp, const Px& p, bool pfin, const float4& cq, const float4& gq, float k,
+                                    float& sw, f3& sum) {
+  if (px_id(cq) != px_id(p.c) || !finite3(cq)) return;  // a miss, outside the image, another BVH record, or not finite
+  const float dot = p.g.x * gq.x + p.g.y * gq.y + p.g.z * gq.z;
+  float wn = dot > 0.0f ? dot : 0.0f;
+  for (int i = 0; i < dp.nsq; ++i) wn = wn * wn;
+  const float xz = __builtin_fabsf(p.g.w - gq.w) / (dp.sigma_d * (p.g.w + gq.w));
+  const float wz = 1.0f / ((1.0f + xz) * (1.0f + xz));
+  float wc = 1.0f;
+  if (pfin) {
+    const float dx = p.c.x - cq.x, dy = p.c.y - cq.y, dz = p.c.z - cq.z;
+    const float xc = (dx * dx + dy * dy + dz * dz) / (dp.sigma_c * dp.sigma_c);
+    wc = 1.0f / ((1.0f + xc) * (1.0f + xc));
+  }
+  const float w = ((k * wn) * wz) * wc;
+  if (!(w > 0.0f)) return;
+  sw += w;
+  sum.x += w * cq.x;
+  sum.y += w * cq.y;
+  sum.z += w * cq.z;
+}
+
+__device__ __forceinline__ float tap_h(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
+
+__device__ __forceinline__ f3 resolve(const Px& p, float sw, f3 sum) {
+  return sw > 0.0f ? mk(sum.x / sw, sum.y / sw, sum.z / sw) : mk(p.c.x, p.c.y, p.c.z);
+}
+
+template <bool FIRST>
+__device__ __forceinline__ void store_px(const DParams& dp, int i, const Px& p, f3 c) {
+  if constexpr (FIRST) dp.guide[i] = p.g;
+  if (dp.dst) dp.dst[i] = make_float4(c.x, c.y, c.z, p.c.w);
+  if (dp.out32) dp.out32[i] = make_float4(c.x, c.y, c.z, 1.0f);
+  if (dp.out8) {
+    const uint32_t r = to_unorm8(linearToSrgb(c.x)), g = to_unorm8(linearToSrgb(c.y)), b = to_unorm8(linearToSrgb(c.z));
+    dp.out8[i] = r | (g << 8) | (b << 16) | (255u << 24);
+  }
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(kBlock) void denoise_tiled_kernel(DParams dp) {
+  const int s = dp.step, halo = 2 * s;
+  const int sw_px = kTileW + 2 * halo, sh_px = kTileH + 2 * halo, n = sw_px * sh_px;
+  float4* lc = g_smem;      // colour | id of the staged pixels, row-major
+  float4* lg = g_smem + n;  // normal | t
+  const int x0 = (int)blockIdx.x * kTileW - halo, y0 = (int)blockIdx.y * kTileH - halo;
+  for (int i = (int)threadIdx.x; i < n; i += kBlock) {
+    const int sy = i / sw_px, sx = i - sy * sw_px;
+    const int gx = x0 + sx, gy = y0 + sy;
+    Px q;
+    q.c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMissId));
+    q.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (gx >= 0 && gx < dp.W && gy >= 0 && gy < dp.H) q = load_px<FIRST>(dp, gy * dp.W + gx);
+    lc[i] = q.c;
+    lg[i] = q.g;
+  }
+  __syncthreads();
+  const int tx = (int)threadIdx.x & (kTileW - 1), ty = (int)threadIdx.x / kTileW;
+  const int x = (int)blockIdx.x * kTileW + tx, y = (int)blockIdx.y * kTileH + ty;
+  if (x >= dp.W || y >= dp.H) return;
+  const int ci = (ty + halo) * sw_px + tx + halo;
+  Px p;
+  p.c = ld16(lc + ci);
+  p.g = ld16(lg + ci);
+  float sw = 0.0f;
+  f3 sum = mk(0.0f, 0.0f, 0.0f);
+  if (px_id(p.c) != kMissId) {
+    const bool pfin = finite3(p.c);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+      for (int dx = -2; dx <= 2; ++dx) {
+        const int qi = ci + dy * s * sw_px + dx * s;
+        tap(dp, p, pfin, ld16(lc + qi), ld16(lg + qi), tap_h(dx) * tap_h(dy), sw, sum);
+      }
+    }
+  }
+  store_px<FIRST>(dp, y * dp.W + x, p, resolve(p, sw, sum));
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(kBlock) void denoise_direct_kernel(DParams dp) {
+  const int x = (int)blockIdx.x * kDirectW + ((int)threadIdx.x & (kDirectW - 1));
+  const int y = (int)blockIdx.y * kDirectH + (int)threadIdx.x / kDirectW;
+  if (x >= dp.W || y >= dp.H) return;
+  const int pi = y * dp.W + x;
+  const Px p = load_px<FIRST>(dp, pi);
+  float sw = 0.0f;
+  f3 sum = mk(0.0f, 0.0f, 0.0f);
+  if (px_id(p.c) != kMissId) {
+    const bool pfin = finite3(p.c);
+    const int s = dp.step;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+      const int qy = y + dy * s;
+#pragma unroll
+      for (int dx = -2; dx <= 2; ++dx) {
+        const int qx = x + dx * s;
+        if (qx < 0 || qx >= dp.W || qy < 0 || qy >= dp.H) continue;
+        const Px q = load_px<FIRST>(dp, qy * dp.W + qx);
+        tap(dp, p, pfin, q.c, q.g, tap_h(dx) * tap_h(dy), sw, sum);
+      }
+    }
+  }
+  store_px<FIRST>(dp, pi, p, resolve(p, sw, sum));
+}
+
+// passes == 0: the mean and the outputs alone (accumulate_kernel's output stage).
+__global__ __launch_bounds__(kBlock) void denoise_resolve_kernel(DParams dp) {
+  const int i = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (i >= dp.W * dp.H) return;
+  const float4 a = dp.src[i];
+  const f3 o = mk(a.x, a.y, a.z) / dp.frames;
+  Px p;
+  p.c = make_float4(o.x, o.y, o.z, 0.0f);
+  p.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  store_px<false>(dp, i, p, o);
+}
+
+struct RayParams {
+  float4* rays;  // 2 float4 per srt_ray: origin | pad0, direction | intersection_distance
+  int W, H;
+  float o[3], p00[3], du[3], dv[3];
+};
+
+__global__ __launch_bounds__(kBlock) void primary_rays_kernel(RayParams rp) {
+  const int p = (int)(blockIdx.x * kBlock + threadIdx.x);
+  if (p >= rp.W * rp.H) return;
+  const int j = p / rp.W, i = p - j * rp.W;
+  const float fi = (float)i, fj = (float)j;
+  const float dx = ((rp.p00[0] + fi * rp.du[0]) + fj * rp.dv[0]) - rp.o[0];
+  const float dy = ((rp.p00[1] + fi * rp.du[1]) + fj * rp.dv[1]) - rp.o[1];
+  const float dz = ((rp.p00[2] + fi * rp.du[2]) + fj * rp.dv[2]) - rp.o[2];
+  rp.rays[2 * (size_t)p] = make_float4(rp.o[0], rp.o[1], rp.o[2], 0.0f);
+  rp.rays[2 * (size_t)p + 1] = make_float4(dx, dy, dz, 1e30f);
+}
+
+}  // namespace denoise
+}  // namespace srt

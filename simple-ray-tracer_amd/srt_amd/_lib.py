@@ -202,6 +202,27 @@ _QUERY_SIGS = {
 }
 QUERY_SYMBOLS = tuple(_QUERY_SIGS)
 
+
+class DenoiseParams(C.Structure):
+    """srt_denoise_params (include/srt_denoise.h)."""
+    _fields_ = [("passes", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_color", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
+# include/srt_denoise.h: the denoiser (its own header and version)
+_DENOISE_SIGS = {
+    "srt_denoise_abi_version": (C.c_int, []),
+    "srt_denoise_create": (C.c_int, [C.c_int, P, C.c_int, C.c_int, C.POINTER(P)]),
+    "srt_denoise_destroy": (C.c_int, [P]),
+    "srt_denoise_stream": (P, [P]),
+    "srt_denoise_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_denoise_get_params": (C.c_int, [P, C.POINTER(DenoiseParams)]),
+    "srt_denoise_set_params": (C.c_int, [P, C.POINTER(DenoiseParams)]),
+    "srt_denoise_primary_rays": (C.c_int, [P, P, P, P, P, P]),
+    "srt_denoise_run": (C.c_int, [P, P, C.c_int, P, P, P]),
+}
+DENOISE_SYMBOLS = tuple(_DENOISE_SIGS)
+
 _lib = None
 
 
@@ -233,7 +254,7 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in _QUERY_SIGS.items():
+        for name, (res, args) in list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,7 +1,7 @@
 """Render a scene to an image file on the GPU: the reference's progressive loop, headless.
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
-                              [--max-depth D] [--out frame.png]
+                              [--max-depth D] [--out frame.png] [--denoise]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -25,6 +25,9 @@ def main():
     ap.add_argument("--max-depth", type=int, default=5)
     ap.add_argument("--synthetic-tris", type=int, default=1_000_000)
     ap.add_argument("--out", default="frame.png")
+    ap.add_argument("--denoise", action="store_true",
+                    help="also write <out>_denoised.<ext>: the frame through the edge-avoiding filter, guided by a "
+                         "closest-hit query of the pixel-centre rays (mesh scenes; sphere pixels pass unfiltered)")
     a = ap.parse_args()
     if a.scene == "rubik":
         models, show = [R.rubik_model(ROOT / "tests" / "golden" / "objects")], True
@@ -47,9 +50,37 @@ def main():
         r.finish()
         dt = time.perf_counter() - t0
         r.compute.save_image(a.out)
+        if a.denoise:
+            denoised = denoise(r, setup, a.out)
     finally:
         r.close()
     print(f"{a.out}: {a.width}x{a.height} @ {a.spp} spp in {dt:.3f} s")
+    if a.denoise:
+        print(f"{denoised}: filtered")
+
+
+def denoise(r, setup, out):
+    """The finished frame of Renderer `r` through srt_amd.denoise.Denoiser, written beside `out`."""
+    import srt_amd as S
+    from srt_amd.denoise import Denoiser
+    from srt_amd.query import Query
+
+    out = pathlib.Path(out)
+    path = out.with_name(out.stem + "_denoised" + out.suffix)
+    acc_ptr, _ = r.compute.image_pointers()
+    with Denoiser(setup.width, setup.height) as dn:
+        hits = None
+        if setup.scene is not None:
+            with Query(setup.scene) as q:
+                q.set_bvh_count(setup.bvh_count)
+                hits = q.closest(dn.primary_rays(setup.camera))
+                q.synchronize()
+        else:
+            dn.set_params(passes=0)  # a sphere scene has no mesh to query: the frame passes through
+        _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
+        dn.synchronize()
+        S.write_image(path, rgba8.cpu().numpy())
+    return path
 
 
 if __name__ == "__main__":
