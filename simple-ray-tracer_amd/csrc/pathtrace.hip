@@ -1,6 +1,7 @@
 // pathtrace.hip -- the kernel-launching part of the device context behind the C ABI (context.hpp): scene
-// and texture uploads, launches of the kernels in kernels.hpp.  context.cpp holds the host-only part,
-// scene_layout.cpp the validation and the node / triangle layouts the upload writes.
+// and texture uploads, launches of the kernels in kernels.hpp.  Only the code that talks to the device:
+// context.cpp holds the host-only part of the context, launch_plan.cpp a launch's LDS layout and chunks,
+// scene_image.cpp the arrays an upload sends, scene_layout.cpp the validation and the node / triangle layouts.
 //
 // Kernels (kernels.hpp; DESIGN.md sections 4-5):
 //   sample_kernel      persistent: waves claim 64-item batches (an 8x8 tile of
@@ -24,7 +25,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstdio>
 #include <cstddef>
 #include <cstring>
@@ -36,13 +36,15 @@
 #include "wavefront.hpp"
 
 #include "context.hpp"
+#include "launch_plan.hpp"
+#include "scene_image.hpp"
 #include "scene_layout.hpp"
 
 // ===========================================================================
 // host side: the launches behind the C ABI
 // ===========================================================================
 using srt::EnsureBvhs, srt::EnsureLights, srt::FreeDev, srt::HipFail, srt::LocalRows, srt::Quiesce, srt::WaitLaunchIdle;
-using srt::LayoutNodes, srt::LayoutTris, srt::TopRegionSlots, srt::ValidateNodes;
+using srt::ValidateNodes;
 
 namespace {
 
@@ -190,8 +192,6 @@ int FillParams(srt_context* c, srt::KParams* kp, bool need_images) {
   return SRT_OK;
 }
 
-// LDS budget per CU (gfx950: 160 KiB; one 1024-thread block per CU in LDS mode)
-constexpr size_t kLdsBytes = 160 * 1024;
 // LDS mode's block (one per CU, the scene copied into its LDS): 1024 threads = 4 waves per SIMD.  An
 // experiment build with 768 (3 waves per SIMD) measures what a wave per SIMD is worth
 #ifndef SRT_LDS_BLOCK
@@ -207,37 +207,34 @@ constexpr int kLdsBlock = SRT_LDS_BLOCK;
 #endif
 constexpr int kGw5Block = SRT_GW5_BLOCK;
 static_assert(kGw5Block % 64 == 0 && 1280 % kGw5Block == 0, "SRT_GW5_BLOCK: 64-lane waves, 1280 lanes per CU");
-// Lanes per block of a global-scene launch of `gw` waves per SIMD (timed fused instance or not)
-constexpr int GlobalBlock(bool timed_fused, int gw) { return (timed_fused && gw == 5) ? kGw5Block : 256; }
-// gfx950 hands a block its LDS in units of 1/128 of the CU's 160 KiB (1,280 B), so n blocks run together
-// only when each asks at most floor(128 / n) units: 5 blocks fit at 32,000 B each, not at 32,001, while
-// hipOccupancyMaxActiveBlocksPerMultiprocessor still answers 5 up to 32,768 (and 3, 6, 7 likewise past their
-// limits; tools/probes/lds_fit.hip, profiles/r06_experiments/lds_fit.json).  The blocks per CU a launch's LDS
-// size allows:
-constexpr size_t kLdsGran = kLdsBytes / 128;
-constexpr int LdsBlocksPerCu(size_t lds) { return lds == 0 ? 1 << 30 : (int)(128 / ((lds + kLdsGran - 1) / kLdsGran)); }
-// The occupancy API's resident blocks per CU, capped by that allocation rule
-static int ResidentPerCu(int api_per_cu, size_t lds) { return std::max(1, std::min(api_per_cu, LdsBlocksPerCu(lds))); }
-// The LDS one such block may take: its whole units of the CU's 160 KiB at gw waves per SIMD (4 SIMDs x 64
-// lanes, gw * 256 / block blocks per CU)
-constexpr size_t GlobalBlockLds(int block, int gw) { return (128 / ((size_t)gw * 256 / (size_t)block)) * kLdsGran; }
-static_assert(GlobalBlockLds(256, 5) == 32000 && GlobalBlockLds(256, 4) == 40960 && GlobalBlockLds(640, 5) == 81920,
-              "the LDS shares the probe measured");
+// This build's constants for the host-only plans (launch_plan.hpp, scene_image.hpp), which never see the
+// macros behind them
+constexpr srt::BuildConsts kBuild = {kLdsBlock, kGw5Block, srt::kNodeBlkF4, srt::global_ring(4), srt::global_ring(5),
+                                     SRT_COOP != 0, srt::kCoopWaveBytes, srt::kCoopIdxBits, srt::kPoolTravLanes,
+                                     srt::kNodePad, (uint32_t)srt::kTriPad, srt::kTreeletCnt};
+
+// Resident blocks per CU of kernel `fn` at `block` lanes and `lds` bytes: the occupancy API's answer capped
+// by the LDS allocation rule (ResidentPerCu), queried once per (kernel instance, LDS size) -- the query
+// runs on the host between the launch's timing events otherwise
+template <typename F>
+int ResidentBlocks(srt_context* c, F* fn, int block, size_t lds, int* per_cu) {
+  const void* key = reinterpret_cast<const void*>(fn);
+  *per_cu = 0;
+  for (const auto& e : c->occupancy)
+    if (e.fn == key && e.lds == lds) *per_cu = e.per_cu;
+  if (*per_cu == 0) {
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, block, lds));
+    *per_cu = srt::ResidentPerCu(*per_cu, lds);
+    c->occupancy.push_back({key, lds, *per_cu});
+  }
+  return SRT_OK;
+}
 
 template <bool COUNT, bool LDSM, bool PACK, int BLOCK, bool TEX, bool FUSE = false, int GW = 4>
 int LaunchSamples(srt_context* c, srt::KParams kp, size_t lds) {
-  // resident blocks per CU, queried once per (kernel instance, LDS size): the
-  // query runs on the host between the launch's timing events otherwise
-  const void* fn = reinterpret_cast<const void*>(&srt::sample_kernel<COUNT, LDSM, PACK, BLOCK, TEX, FUSE, GW>);
   int per_cu = 0;
-  for (const auto& e : c->occupancy)
-    if (e.fn == fn && e.lds == lds) per_cu = e.per_cu;
-  if (per_cu == 0) {
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, srt::sample_kernel<COUNT, LDSM, PACK, BLOCK, TEX, FUSE, GW>,
-                                                          BLOCK, lds));
-    per_cu = ResidentPerCu(per_cu, lds);
-    c->occupancy.push_back({fn, lds, per_cu});
-  }
+  if (int ro = ResidentBlocks(c, &srt::sample_kernel<COUNT, LDSM, PACK, BLOCK, TEX, FUSE, GW>, BLOCK, lds, &per_cu))
+    return ro;
   const int blocks = c->num_cus * per_cu;
   c->launch_per_cu = per_cu;
   c->launch_block = BLOCK;
@@ -296,15 +293,8 @@ int LaunchSamples(srt_context* c, srt::KParams kp, size_t lds) {
 // so its LDS holds only the light records).
 template <bool COUNT>
 int LaunchSpheres(srt_context* c, srt::KParams kp, size_t lds) {
-  const void* fn = reinterpret_cast<const void*>(&srt::sphere_kernel<COUNT>);
   int per_cu = 0;
-  for (const auto& e : c->occupancy)
-    if (e.fn == fn && e.lds == lds) per_cu = e.per_cu;
-  if (per_cu == 0) {
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, srt::sphere_kernel<COUNT>, 256, lds));
-    per_cu = ResidentPerCu(per_cu, lds);
-    c->occupancy.push_back({fn, lds, per_cu});
-  }
+  if (int ro = ResidentBlocks(c, &srt::sphere_kernel<COUNT>, 256, lds, &per_cu)) return ro;
   // resident blocks per CU: as many as its registers allow (C2 on one box, ms per launch: 3 blocks 3.23,
   // 4 3.00, 5 2.93; while the launch counter's atomic rate bound it, round 3, 3 were best)
   const int blocks = c->num_cus * std::min(per_cu, c->sphere_blocks);
@@ -362,15 +352,8 @@ int LaunchPool(srt_context* c, srt::KParams kp, size_t lds) {
 // sub-steps or the IL pattern, waves per SIMD) and their grids: as many 256-lane blocks as are resident.
 template <typename F>
 int Resident(srt_context* c, F* fn, size_t lds, int* blocks) {
-  const void* key = reinterpret_cast<const void*>(fn);
   int per_cu = 0;
-  for (const auto& e : c->occupancy)
-    if (e.fn == key && e.lds == lds) per_cu = e.per_cu;
-  if (per_cu == 0) {
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
-    per_cu = ResidentPerCu(per_cu, lds);
-    c->occupancy.push_back({key, lds, per_cu});
-  }
+  if (int ro = ResidentBlocks(c, fn, 256, lds, &per_cu)) return ro;
   *blocks = c->num_cus * per_cu;
   return SRT_OK;
 }
@@ -573,13 +556,6 @@ int LaunchWavefront(srt_context* c, srt::KParams kp, bool tex) {
   return SRT_OK;
 }
 
-// LDS bytes of the light records a launch keeps in LDS (behind the rest of its layout, when they fit the
-// kernel's cap, as Launch places them)
-size_t LightLdsBytes(const srt::KParams& kp) {
-  const size_t light_bytes = 2 * sizeof(float4) * ((size_t)kp.light_records + 1);
-  return light_bytes <= 8192 ? light_bytes : 0;
-}
-
 // Runs frames kp.frame_first .. + kp.nframes - 1 (or the reset frame) through
 // sample_kernel + accumulate_kernel, in chunks that fit the sample buffer.
 int Launch(srt_context* c, srt::KParams& kp, bool count) {
@@ -592,115 +568,52 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
     return SRT_OK;
   }
   if (kp.nframes <= 0) return SRT_OK;
-  // LDS mode: the whole scene + 1024 lanes' 2-dword stacks fit in one CU's LDS
-  // (node pairs at the padded LDS stride; only for node arrays whose pairs are all 64-B aligned)
-  const size_t scene_bytes = ((size_t)kp.nodes_lds_f4 + (size_t)kp.tris_f4) * sizeof(float4);
-  const size_t lds_mode_bytes = scene_bytes + (size_t)kLdsBlock * 2 * sizeof(uint32_t) * (size_t)kp.stack_entries;
-  const bool ldsm = kp.show_model && c->lds_ok && c->pairs_aligned && !c->force_global && lds_mode_bytes <= kLdsBytes;
-  const int gw = (!count && c->fused) ? c->global_waves : 4;  // global-scene mode: LaunchMode's instance
-  const int block = ldsm ? kLdsBlock : GlobalBlock(!count && c->fused, gw);
-  // pool mode (pool.hpp): LDS mode with stacks for the traversal waves only, then the ray records;
-  // laid out first, and sample_kernel's layout when the records do not fit
-  bool pool = ldsm && c->pool && !c->sample_textures && kp.max_depth >= 0 && kp.max_depth <= 255;
-  size_t lds = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (pool) {
-      kp.stack_base_f4 = kp.nodes_lds_f4 + kp.tris_f4;
-      lds = scene_bytes + (size_t)srt::kPoolTravLanes * 2 * sizeof(uint32_t) * (size_t)kp.stack_entries;
-    } else if (ldsm) {
-      kp.stack_base_f4 = kp.nodes_lds_f4 + kp.tris_f4;
-      lds = lds_mode_bytes;
-    } else if (kp.show_model) {  // LDS rings of global_ring(waves) entries per lane, backed by HBM stacks
-      kp.stack_base_f4 = 0;
-      lds = (size_t)block * (c->lds_ok ? 2 : 3) * sizeof(uint32_t) * (size_t)srt::global_ring(gw);
-      if (SRT_COOP && !count && c->fused) {  // the fused sub-steps' load stages, one per wave
-        lds = (lds + 15) & ~(size_t)15;
-        kp.coop_off = (int)lds;
-        lds += (size_t)(block / 64) * srt::kCoopWaveBytes;
-      }
-      // the top levels' pairs (LayoutNodes' first region) for the fused instance, when they fit beside the
-      // rings and this launch's light records (placed behind it, below) within the LDS one of the
-      // instance's blocks may take; the material records follow only if they still fit that share, else
-      // shading reads them from HBM, so neither costs a resident block per CU, and the region,
-      // worth ~10% on a surface mesh, is never given up for them; wavefront mode's kernels read none
-      kp.top_f4 = 0;
-      const bool wf_launch = !count && (c->wavefront >= 0 ? c->wavefront == 1 : c->wf_scene);
-      if (!count && c->fused && !wf_launch && c->top_f4 > 0) {
-        lds = (lds + 15) & ~(size_t)15;
-        const size_t tb = ((size_t)c->top_f4 + 3) / 4 * srt::kNodeBlkF4 * sizeof(float4);
-        if (lds + tb + LightLdsBytes(kp) <= GlobalBlockLds(block, gw)) {
-          kp.top_f4 = c->top_f4;
-          kp.top_lds_f4 = (int)(lds / sizeof(float4));
-          lds += tb;
-        }
-      }
-      c->launch_top_f4 = kp.top_f4;
-    } else {  // the sphere scene (sphere_kernel): no traversal stacks
-      kp.stack_base_f4 = 0;
-      lds = 0;
-    }
-    {  // light and material records in LDS behind the rest, when they fit (shading reads them there) within
-       // the LDS one block may take: all of it in LDS mode, a global-scene block's share at its instance's
-       // blocks per CU (records past it would cost a resident block per CU; they are read from HBM instead)
-      const size_t cap = (!ldsm && kp.show_model) ? GlobalBlockLds(block, gw) : kLdsBytes;
-      lds = (lds + 15) & ~(size_t)15;
-      const size_t light_bytes = 2 * sizeof(float4) * ((size_t)kp.light_records + 1);
-      kp.lights_lds = (light_bytes <= 8192 && lds + light_bytes <= cap) ? 1 : 0;
-      if (kp.lights_lds) {
-        kp.lights_base_f4 = (int)(lds / sizeof(float4));
-        lds += light_bytes;
-      }
-      kp.mat_records = (int)c->n_mats + 1;
-      const size_t mat_bytes = 2 * sizeof(float4) * (size_t)kp.mat_records;
-      kp.mats_lds = (kp.show_model && c->d_mats && mat_bytes <= 16384 && lds + mat_bytes <= cap) ? 1 : 0;
-      if (kp.mats_lds) {
-        kp.mats_base_f4 = (int)(lds / sizeof(float4));
-        lds += mat_bytes;
-      }
-      c->launch_mats_lds = kp.mats_lds;
-    }
-    if (!pool) break;
-    // control words, 3 rings of u32 record ids (power-of-two capacity), 112-B records
-    kp.pool_ctl_off = (int)lds;
-    lds += 16 * sizeof(uint32_t);
-    int slots = 0, cap = 1;
-    for (int r = std::min(c->pool_slots_max, 65534); r >= 64 && slots == 0; --r) {
-      int cp = 1;
-      while (cp < r) cp <<= 1;
-      if (lds + (size_t)3 * cp * sizeof(uint32_t) + (size_t)r * 112 <= kLdsBytes) {
-        slots = r;
-        cap = cp;
-      }
-    }
-    if (slots == 0) {  // no room for 64 records
-      pool = false;
-      continue;
-    }
-    kp.pool_ring_off = (int)lds;
-    lds += (size_t)3 * cap * sizeof(uint32_t);
-    kp.pool_rec_off = (int)lds;
-    lds += (size_t)slots * 112;
-    kp.pool_cap = cap;
-    kp.pool_slots = slots;
+  // the launch's LDS layout and its chunks of frames (launch_plan.hpp)
+  srt::LdsPlanIn in{};
+  in.show_model = kp.show_model != 0;
+  in.count = count;
+  in.lds_ok = c->lds_ok;
+  in.pairs_aligned = c->pairs_aligned;
+  in.force_global = c->force_global;
+  in.fused = c->fused;
+  in.global_waves = c->global_waves;
+  in.pool = c->pool && !c->sample_textures && kp.max_depth >= 0 && kp.max_depth <= 255;
+  in.pool_slots_max = c->pool_slots_max;
+  in.wavefront = c->wavefront >= 0 ? c->wavefront == 1 : c->wf_scene;
+  in.nodes_lds_f4 = kp.nodes_lds_f4;
+  in.tris_f4 = kp.tris_f4;
+  in.stack_entries = kp.stack_entries;
+  in.light_records = kp.light_records;
+  in.n_mats = c->n_mats;
+  in.has_mats = c->d_mats != nullptr;
+  in.top_f4 = c->top_f4;
+  const srt::LdsPlan plan = srt::PlanLds(kBuild, in);
+  const bool ldsm = plan.ldsm, pool = plan.pool, wf = plan.wf;
+  const size_t lds = plan.lds;
+  kp.stack_base_f4 = plan.stack_base_f4;
+  kp.coop_off = plan.coop_off;
+  kp.top_f4 = plan.top_f4;
+  kp.top_lds_f4 = plan.top_lds_f4;
+  kp.lights_lds = plan.lights_lds;
+  kp.lights_base_f4 = plan.lights_base_f4;
+  kp.mats_lds = plan.mats_lds;
+  kp.mat_records = plan.mat_records;
+  kp.mats_base_f4 = plan.mats_base_f4;
+  if (!ldsm && kp.show_model) c->launch_top_f4 = plan.top_f4;  // (of the last global-scene launch)
+  c->launch_mats_lds = plan.mats_lds;
+  if (pool) {
+    kp.pool_ctl_off = plan.pool_ctl_off;
+    kp.pool_ring_off = plan.pool_ring_off;
+    kp.pool_rec_off = plan.pool_rec_off;
+    kp.pool_cap = plan.pool_cap;
+    kp.pool_slots = plan.pool_slots;
     kp.pool_batch = c->pool_batch;
     kp.pool_tlow = c->pool_tlow;
     kp.pool_deadline = (unsigned long long)c->pool_deadline_ms * 100000ull;  // s_memrealtime runs at 100 MHz
-    break;
   }
-  // sample buffer: as many frames per chunk as the buffer cap allows
-  const size_t per_frame = (size_t)npx * sizeof(float4);
-  // frames per launch: what the sample buffer holds, and n_tiles * frames < 2^31 (the kernel's batch index)
-  const size_t n_tiles = (size_t)((kp.W + 7) >> 3) * (size_t)((kp.local_rows + 7) >> 3);
-  // (less 2^20: the batch counter overshoots the end by up to (max(kClaim, kClaimSph) + 1) claims per wave)
-  // wavefront mode (global-scene, timed launches): its sample items (64 per batch) < 2^31 per chunk
-  const bool wf = !ldsm && !count && kp.show_model && (c->wavefront >= 0 ? c->wavefront == 1 : c->wf_scene);
-  const size_t max_frames = std::max<size_t>(
-      1, ((size_t)0x7FFFFFFF - ((size_t)1 << 20)) / std::max<size_t>(1, n_tiles) / (wf ? 64 : 1));
-  // the context's sample buffers share SRT_SAMPLE_BUFFER_MB: its own and, with pipeline slots, one per slot
-  const size_t lbuf_cap = c->lbuf_total / (size_t)(c->pipe > 1 ? c->pipe + 1 : 1);
-  const int chunk = (int)std::max<size_t>(
-      1, std::min<size_t>(std::min<size_t>((size_t)kp.nframes, max_frames), lbuf_cap / per_frame));
-  const size_t need = per_frame * (size_t)chunk;
+  const srt::ChunkPlan chunks = srt::PlanChunks(kp.W, kp.local_rows, npx, kp.nframes, wf, c->lbuf_total, c->pipe);
+  const size_t n_tiles = chunks.n_tiles, need = chunks.need;
+  const int chunk = chunks.chunk, nchunks = chunks.nchunks;
   const bool piped = !count && !pool && !wf && c->pipe > 1;
   // (a counting launch, the untimed first launch of a measurement, sets the slots up for the timed ones)
   if ((piped || (count && c->pipe > 1)) && c->slots.empty()) {
@@ -718,7 +631,6 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
   static_assert(srt::ST_POOLERR + 1 == srt::ST_TOTAL, "ST_POOLERR must stay the last stats entry");
   HIP_OK(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * srt::ST_POOLERR, c->stream));
   const int out_frames = kp.frame_first + kp.nframes - 1;
-  const int nchunks = (kp.nframes + chunk - 1) / chunk;
   while ((int)c->ev.size() < 2 * nchunks) {
     hipEvent_t e;
     HIP_OK(hipEventCreate(&e));
@@ -876,6 +788,15 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
   return SRT_OK;
 }
 
+// One array of a scene image onto the device (`*dst` stays null for an empty one); the caller synchronizes.
+template <typename T>
+int UploadArray(srt_context* c, T** dst, const std::vector<T>& src) {
+  if (src.empty()) return SRT_OK;
+  HIP_OK(hipMalloc(dst, src.size() * sizeof(T)));
+  HIP_OK(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  return SRT_OK;
+}
+
 }  // namespace
 
 namespace srt {
@@ -1015,276 +936,44 @@ int srt_upload_scene(srt_context* c, const srt_bvh_record* bvhs, uint32_t n_bvhs
   int rc = ValidateNodes(nodes, n_nodes, n_tris, bvhs, n_bvhs, &depth, &tri_ranges, &reach);
   if (rc) return rc;
   HIP_OK(hipSetDevice(c->device));
-  // nodes: 32-B records behind a 32-B pad so sibling pairs are 64-B aligned,
-  // in the traversal's order (LayoutNodes; unreachable nodes are dropped), and
-  // one zero pair past the end for the internal step's speculative read
-  std::vector<uint32_t> remap;
-  uint32_t n_slots = n_nodes;
-  const char* lay_env = std::getenv("SRT_NODE_LAYOUT");
-  // Line-aligned chains pay where the tree streams from HBM: fewer lines per
-  // step (C5, 10 M triangles: 505 -> 578 Mrays/s; 3 M: 774 -> 823).  A scene
-  // the 256-MB Infinity Cache holds runs latency-bound and is faster dense
-  // (300 k: 1929 vs 1695; 1 M: 1234 vs 1088), though it then misses more
-  // often in L2.  Measured crossover between 100 and 300 MB of nodes +
-  // triangles; SRT_NODE_ALIGN=1/0 forces either.
-  const char* al_env = std::getenv("SRT_NODE_ALIGN");
-  const double scene_mb = (32.0 * n_nodes + 48.0 * n_tris) / (1 << 20);
-  const bool align = al_env ? al_env[0] == '1' : scene_mb >= 192.0;
-  // Global-scene traversal schedule: fused sub-steps (trav_fused: one memory
-  // round trip per step for both node kinds) while the kernel waits on latency
-  // (1 M, 101 MB: 1232 -> 1373 Mrays/s; 262 k torus knot 4576 -> 5432; 3 M,
-  // 336 MB: 832 -> 869); the IL pattern once the tree streams from HBM and
-  // the bytes bound it (10 M, 1.1 GB, at 1080p: 543 vs 528).  Crossover taken
-  // at 600 MB; SRT_GLOBAL_FUSED_MODE=1/0 forces either.
-  const char* fu_env = std::getenv("SRT_GLOBAL_FUSED_MODE");
-  c->fused = fu_env ? fu_env[0] == '1' : scene_mb < 600.0;
-  // Waves per SIMD of the fused instance: 5 (8-entry rings, some spills) while the tree is small
-  // enough that the extra rays in flight pay (torus knot 262 k, 20 MB: 5,405 -> 5,650 Mrays/s; Rubik
-  // forced global +6%; 100 k +2%; 300 k, 30 MB: +1%), else 4 (1 M, 101 MB: -7% with 5; 3 M: -7%).
-  // Crossover taken at 48 MB; SRT_GLOBAL_WAVES_MODE=4/5 forces either.
-  const char* gw_env = std::getenv("SRT_GLOBAL_WAVES_MODE");
-  c->global_waves = gw_env ? (gw_env[0] == '5' ? 5 : 4) : (scene_mb < 48.0 ? 5 : 4);
-  // Triangle slots (LayoutTris) for every scene read through L2 (none of 1 MB fits the LDS copy):
-  // fewer lines per leaf step (A/B on one box, kernel ms: C5 10 M 4096² 820 -> 773 with the IL leaf
-  // step's own-record reads, 3 M 58.4 -> 56.5, 1 M 34.1 -> 32.6, torus knot 27.4 -> 27.4, Rubik
-  // unchanged).  SRT_TRI_ALIGN=1/0 forces either.  Leaves and each BVH's triangle range are
-  // remapped; a record keeps its triangle's input index (C.z) for the closest-hit query.
-  const char* ta_env = std::getenv("SRT_TRI_ALIGN");
-  const bool tri_align = ta_env ? ta_env[0] == '1' : scene_mb >= 1.0;
-  std::vector<uint32_t> tslot;
-  uint32_t n_tslots = n_tris;
-  // (the slots stay below 3 n_tris: a gap is at most two records per leaf)
-  const bool tris_laid =
-      tri_align && n_tris < (1u << 30) && LayoutTris(nodes, n_nodes, reach, n_tris, &tslot, &n_tslots);
-  uint32_t max_leaf = 0;
-  for (uint32_t i = 0; i < n_nodes; ++i)
-    if (reach[i]) max_leaf = std::max(max_leaf, nodes[i].prim_count);
-  // The fused instance's LDS copy of the tree's top levels (traversal.hpp trav_fused): LDS reads bypass
-  // the vector-memory pipeline that bounds these kernels.  Laid out first, as deep
-  // as fits the LDS one block may take beside its rings and the light records (SRT_TOP_DEPTH=d forces d
-  // levels, 0 none).  The ring's entry size is the one Launch will use
-  // (lds_ok below, with the dense node count: a line-aligned layout's padding only matters past 2^24
-  // slots, where Launch then finds the region too large and skips it).  A depth's region size comes from
-  // the layout's first pass alone (TopRegionSlots, bounded by the depth); the full layout runs once.
-  uint32_t n_top = 0;
-  int top_depth = 0;
-  {
-    const char* td_env = std::getenv("SRT_TOP_DEPTH");
-    if (c->fused && scene_mb >= 1.0 && !(td_env && std::atoi(td_env) <= 0)) {
-      const bool pack = n_tslots < (1u << 24) && n_nodes + srt::kNodePad < (1u << 24) && max_leaf < 256;
-      const int gblock = GlobalBlock(true, c->global_waves);
-      const size_t ring = (size_t)gblock * (pack ? 2 : 3) * sizeof(uint32_t) * (size_t)srt::global_ring(c->global_waves);
-      // beside the light records (the ones set, at least the reference's six, src/main.cpp:584-589, and the
-      // zero record) when they fit their LDS cap, as Launch places them (LightLdsBytes); the material
-      // records take what the region leaves (Launch)
-      const size_t lb = 2 * sizeof(float4) * (std::max<size_t>(c->h_lights.size(), 6) + 1);
-      const size_t lm = lb <= 8192 ? lb : 0;
-      const size_t share = GlobalBlockLds(gblock, c->global_waves);
-      const size_t budget = share > ring + lm + 64 ? share - ring - lm - 64 : 0;
-      top_depth = td_env ? std::atoi(td_env) : 12;
-      for (; top_depth > 0; --top_depth) {  // the deepest whole levels that fit
-        if (!TopRegionSlots(nodes, n_nodes, bvhs, n_bvhs, align, top_depth, &n_top)) {
-          top_depth = 0;
-          break;
-        }
-        if (td_env || ((2 * (size_t)n_top + 2 + 3) / 4) * srt::kNodeBlkF4 * sizeof(float4) <= budget) break;
-      }
-    }
-  }
-  bool laid = !(lay_env && lay_env[0] == '0') &&
-              LayoutNodes(nodes, n_nodes, bvhs, n_bvhs, align, &remap, &n_slots, top_depth, &n_top);
-  if (!laid) n_top = 0;
-  auto tsl = [&](uint32_t t) { return tris_laid ? tslot[t] : t; };
-  for (auto& r : tri_ranges)
-    if (r.first < r.second) r = {tsl(r.first), tsl(r.second - 1) + 1};
-  if (!laid) {
-    remap.resize(n_nodes);
-    for (uint32_t i = 0; i < n_nodes; ++i) remap[i] = i;
-    n_slots = n_nodes;
-  }
-  std::vector<float4> hn(2 * ((size_t)n_slots + 1 + srt::kNodePad), make_float4(0, 0, 0, 0));
-  bool pairs_aligned = true;
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    // (a node no traversal reaches keeps a zero record: its indices were never range-checked)
-    if (remap[i] == 0xFFFFFFFFu || !reach[i]) continue;
-    const srt_bvh_node& n = nodes[i];
-    uint32_t first = n.first_child_or_prim_index;
-    if (n.prim_count == 0) {  // internal: c0's slot, less 1 when c1 is internal (its pair then follows)
-      // The flag promises that c1's own child pair is the next pair of the array.  LayoutNodes
-      // places it there whenever it lays the pair out itself; a pair shared with an earlier
-      // BVH record's tree keeps its first placement, so the flag is set only when the
-      // remapped slots say so.
-      const uint32_t c0 = n.first_child_or_prim_index;
-      const srt_bvh_node& n1 = nodes[c0 + 1];
-      first = remap[first];
-      if (laid && n1.prim_count == 0 && remap[n1.first_child_or_prim_index] == remap[c0] + 2) first -= 1;
-      if (((first | (laid ? 1u : 0u)) & 1u) == 0) pairs_aligned = false;  // overlapping sibling pairs
-    } else {
-      first = tsl(first);
-    }
-    float w0, w1;
-    std::memcpy(&w0, &first, 4);
-    std::memcpy(&w1, &n.prim_count, 4);
-    hn[2 * (size_t)remap[i] + 2] = make_float4(n.min_bounds[0], n.min_bounds[1], n.min_bounds[2], w0);
-    hn[2 * (size_t)remap[i] + 3] = make_float4(n.max_bounds[0], n.max_bounds[1], n.max_bounds[2], w1);
-  }
-  // Treelet scheduling (wavefront mode, wavefront.hpp): a copy of the node array in which every internal
-  // node at depth td of some tree (walked from every BVH root and from slot 0, where the ghost records
-  // start) is a treelet root -- its count kTreeletCnt, its child index the treelet's id -- and whose
-  // nodes with a treelet root as right child lose the right-spine flag (the top kernel must make the root
-  // current, not expand it).  Every path deeper than td passes a root, so the top-level stack holds < td
-  // entries.  Chosen for trees past the Infinity Cache, with ~1 MB treelets (SRT_TREELETS=1/0 forces it,
-  // SRT_TREELET_DEPTH sets td).
+  // what the scene's size chooses, and the arrays and scalars of the device layout (scene_image.hpp)
+  const srt::ScenePolicy policy = srt::ChooseScenePolicy(n_nodes, n_tris, c->treelet_depth, c->treelets);
+  const srt::SceneArrays in{bvhs, n_bvhs, nodes, n_nodes, mats, tex_albedo, n_mats, tris, n_tris, verts, n_verts};
+  srt::SceneImage img;
+  srt::BuildSceneImage(in, depth, std::move(tri_ranges), reach, policy, kBuild, c->h_lights.size(), &img);
+  c->global_waves = policy.global_waves;
+  c->tl_scene = policy.tl_scene;
   FreeDev(c->d_nodes_t);
   FreeDev(c->d_troot);
   c->d_nodes_t = nullptr;
   c->d_troot = nullptr;
   c->n_treelets = 0;
-  {
-    uint32_t max_leaf_in = 0;
-    for (uint32_t i = 0; i < n_nodes; ++i)
-      if (reach[i]) max_leaf_in = std::max(max_leaf_in, nodes[i].prim_count);
-    int td = c->treelet_depth;
-    if (td == 0) {  // ~1 MB of nodes + triangles per treelet
-      td = 1;
-      while (td < srt::kTopStack - 1 && scene_mb / (double)(1u << (td + 1)) >= 1.0) ++td;
-    }
-    c->tl_scene = false;  // opt-in (measured slower than sample_kernel: DESIGN.md section 5, "Wavefront mode")
-    const bool want = c->treelets >= 0 ? c->treelets == 1 : c->tl_scene;
-    if (want && max_leaf_in < srt::kTreeletCnt && depth > td) {
-      std::vector<float4> hf(hn);
-      std::vector<uint32_t> troot;
-      std::vector<int32_t> tid_of(n_slots, -1);
-      auto u32 = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-      auto f32 = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-      std::vector<uint32_t> roots{0};
-      for (uint32_t b = 0; b < n_bvhs; ++b) roots.push_back(remap[bvhs[b].first_index]);
-      std::vector<std::pair<uint32_t, int>> st;
-      const uint32_t ror = laid ? 1u : 0u;
-      for (uint32_t r : roots) {
-        st.push_back({r, 0});
-        while (!st.empty()) {
-          auto [sl, d] = st.back();
-          st.pop_back();
-          if (u32(hn[2 * (size_t)sl + 3].w) != 0u || tid_of[sl] >= 0) continue;  // a leaf, or a root already
-          const uint32_t first = u32(hn[2 * (size_t)sl + 2].w);
-          if (d == td) {
-            tid_of[sl] = (int32_t)troot.size();
-            troot.push_back(first);
-            hf[2 * (size_t)sl + 2].w = f32((uint32_t)tid_of[sl]);
-            hf[2 * (size_t)sl + 3].w = f32(srt::kTreeletCnt);
-            continue;
-          }
-          const uint32_t ref0 = first | ror;
-          st.push_back({ref0, d + 1});
-          st.push_back({ref0 + 1, d + 1});
-        }
-      }
-      for (uint32_t sl = 0; sl < n_slots && ror; ++sl) {  // no right-spine step onto a treelet root
-        const uint32_t first = u32(hn[2 * (size_t)sl + 2].w);
-        if (tid_of[sl] >= 0 || u32(hn[2 * (size_t)sl + 3].w) != 0u || (first & 1u)) continue;
-        if (first + 2 < n_slots && tid_of[first + 2] >= 0) hf[2 * (size_t)sl + 2].w = f32(first | 1u);
-      }
-      if (!troot.empty()) {
-        HIP_OK(hipMalloc(&c->d_nodes_t, hf.size() * sizeof(float4)));
-        HIP_OK(hipMalloc(&c->d_troot, troot.size() * sizeof(uint32_t)));
-        HIP_OK(hipMemcpyAsync(c->d_nodes_t, hf.data(), hf.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->d_troot, troot.data(), troot.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                              c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        c->n_treelets = (uint32_t)troot.size();
-      }
-    }
-  }
-  // materials -> shading materials (raytrace_utils.glsl:140-175); one zero
-  // record appended for out-of-range material indices (OOB SSBO reads = 0)
-  std::vector<float4> hm(2 * ((size_t)n_mats + 1), make_float4(0, 0, 0, 0));
-  bool sampled = false;
-  for (uint32_t i = 0; i <= n_mats; ++i) {
-    srt_material_obj m{};
-    if (i < n_mats) m = mats[i];
-    float alb[3] = {m.diffuse[0], m.diffuse[1], m.diffuse[2]};
-    uint32_t tex = 0;  // sampled texture + 1 (0: constant albedo)
-    if (m.use_texture) {
-      for (int k = 0; k < 3; ++k) alb[k] = tex_albedo ? tex_albedo[3 * (size_t)i + k] : 0.0f;
-      if (!tex_albedo) {
-        const uint64_t h = (uint64_t)m.handle[0] | ((uint64_t)m.handle[1] << 32);
-        tex = h < 0xFFFFFFFFull ? (uint32_t)h + 1 : 0xFFFFFFFFu;  // unknown handles sample zero
-        sampled = true;
-      }
-    }
-    const float rough = 1.0f / (m.specular_ex + 0.0000001f);
-    float tf;
-    std::memcpy(&tf, &tex, 4);
-    hm[2 * (size_t)i] = make_float4(alb[0], alb[1], alb[2], rough);
-    hm[2 * (size_t)i + 1] = make_float4(m.specular[0], m.specular[1], m.specular[2], tf);
-  }
-  // triangles (at their slots): v0, e1 = v1 - v0, e2 = v2 - v0, material, input index
-  // kTriPad zero records past the end: a multi-triangle leaf step may read (and discard) them
-  std::vector<float4> ht(3 * ((size_t)n_tslots + srt::kTriPad), make_float4(0, 0, 0, 0));
-  auto vert = [&](uint32_t i, int k) -> float { return i < n_verts ? verts[i].vertex[k] : 0.0f; };
-  for (uint32_t t = 0; t < n_tris; ++t) {
-    const size_t st = tsl(t);
-    const srt_triangle& tr = tris[t];
-    float v0[3], e1[3], e2[3];
-    for (int k = 0; k < 3; ++k) {
-      v0[k] = vert(tr.v0_idx, k);
-      e1[k] = vert(tr.v1_idx, k) - v0[k];
-      e2[k] = vert(tr.v2_idx, k) - v0[k];
-    }
-    const uint32_t mi = tr.material_idx < n_mats ? tr.material_idx : n_mats;
-    float mf, tf;
-    std::memcpy(&mf, &mi, 4);
-    std::memcpy(&tf, &t, 4);
-    ht[3 * st + 0] = make_float4(v0[0], v0[1], v0[2], e1[0]);
-    ht[3 * st + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
-    ht[3 * st + 2] = make_float4(e2[2], mf, tf, 0.0f);
-  }
-  // vertex uvs per triangle, for the materials that sample a texture
-  std::vector<float4> huv;
-  if (sampled) {
-    huv.assign(2 * (size_t)n_tslots, make_float4(0, 0, 0, 0));
-    auto uv = [&](uint32_t i, int k) -> float { return i < n_verts ? verts[i].texture[k] : 0.0f; };
-    for (uint32_t t = 0; t < n_tris; ++t) {
-      const srt_triangle& tr = tris[t];
-      const size_t st = tsl(t);
-      huv[2 * st] = make_float4(uv(tr.v0_idx, 0), uv(tr.v0_idx, 1), uv(tr.v1_idx, 0), uv(tr.v1_idx, 1));
-      huv[2 * st + 1] = make_float4(uv(tr.v2_idx, 0), uv(tr.v2_idx, 1), 0.0f, 0.0f);
-    }
-  }
+  if ((rc = UploadArray(c, &c->d_nodes_t, img.nodes_t))) return rc;
+  if ((rc = UploadArray(c, &c->d_troot, img.troot))) return rc;
+  if (!img.troot.empty()) HIP_OK(hipStreamSynchronize(c->stream));
+  c->n_treelets = (uint32_t)img.troot.size();
   FreeDev(c->d_nodes); FreeDev(c->d_mats); FreeDev(c->d_tris); FreeDev(c->d_tri_uv);
   c->d_nodes = nullptr; c->d_mats = nullptr; c->d_tris = nullptr; c->d_tri_uv = nullptr;
   c->scene_ok = false;
-  if (sampled && n_tris) {
-    HIP_OK(hipMalloc(&c->d_tri_uv, huv.size() * sizeof(float4)));
-    HIP_OK(hipMemcpyAsync(c->d_tri_uv, huv.data(), huv.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_OK(hipMalloc(&c->d_nodes, hn.size() * sizeof(float4)));
-  HIP_OK(hipMalloc(&c->d_mats, hm.size() * sizeof(float4)));
-  HIP_OK(hipMalloc(&c->d_tris, ht.size() * sizeof(float4)));
-  HIP_OK(hipMemcpyAsync(c->d_nodes, hn.data(), hn.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipMemcpyAsync(c->d_mats, hm.data(), hm.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-  HIP_OK(hipMemcpyAsync(c->d_tris, ht.data(), ht.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+  if ((rc = UploadArray(c, &c->d_tri_uv, img.tri_uv))) return rc;
+  if ((rc = UploadArray(c, &c->d_nodes, img.nodes))) return rc;
+  if ((rc = UploadArray(c, &c->d_mats, img.mats))) return rc;
+  if ((rc = UploadArray(c, &c->d_tris, img.tris))) return rc;
   HIP_OK(hipStreamSynchronize(c->stream));
-  c->h_bvhs.assign(bvhs, bvhs + n_bvhs);
-  for (auto& r : c->h_bvhs) r.first_index = remap[r.first_index];  // roots in the device layout
-  c->bvh_tris = std::move(tri_ranges);
-  c->sample_textures = sampled;
+  c->h_bvhs = std::move(img.bvhs);
+  c->bvh_tris = std::move(img.bvh_tris);
+  c->sample_textures = img.sampled;
   c->bvhs_dirty = true;
-  c->n_nodes = n_slots + srt::kNodePad;
-  c->top_f4 = n_top > 0 ? 2 * (int)n_top + 2 : 0;  // float4 of slots [0, n_top)
-  c->top_depth = n_top > 0 ? top_depth : 0;
-  c->ref_or = laid ? 1u : 0u;
-  c->n_tris = n_tslots;  // device records (slots)
+  c->n_nodes = img.n_slots + srt::kNodePad;
+  c->top_f4 = img.n_top > 0 ? 2 * (int)img.n_top + 2 : 0;  // float4 of slots [0, n_top)
+  c->top_depth = img.top_depth;
+  c->ref_or = img.ref_or;
+  c->n_tris = img.n_tslots;  // device records (slots)
   c->n_mats = n_mats;
-  c->stack_entries = depth + 1;
-  c->lds_ok = n_tslots < (1u << 24) && n_slots + srt::kNodePad < (1u << 24) && max_leaf < 256;
-  // cooperative loads (SRT_COOP builds) carry a request's float4 index in kCoopIdxBits bits: larger
-  // arrays (only reachable with SRT_GLOBAL_FUSED_MODE=1 past 600 MB) take the IL instance
-  if (SRT_COOP && (2ull * ((uint64_t)c->n_nodes + 1) + 8 >= (1ull << srt::kCoopIdxBits) ||
-                   3ull * ((uint64_t)n_tslots + srt::kTriPad) >= (1ull << srt::kCoopIdxBits)))
-    c->fused = false;
-  c->pairs_aligned = pairs_aligned;
+  c->stack_entries = img.depth + 1;
+  c->lds_ok = img.lds_ok;
+  c->fused = img.fused;
+  c->pairs_aligned = img.pairs_aligned;
   c->scene_ok = true;
   if (c->bvh_count == 0) c->bvh_count = n_bvhs;
   // the zero records beyond n_bvhs traverse from node 0 with a zero ray

@@ -426,3 +426,37 @@ def test_scene_layouts_under_sanitizers():
     r = subprocess.run([str(exe), str(RUBIK)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "Rubik: 1188 triangles, 427 nodes, depth 9" in r.stdout and "scene layout checks OK" in r.stdout
+
+
+def _sanitized_host_program(name, sources, extra=()):
+    """tests/cpp/<name>.cpp with the given csrc files linked directly, AddressSanitizer + UBSan, as a stand-alone
+    program (host code only: no HIP runtime, no device, nothing preloaded)."""
+    from conftest import PKG, ROOT
+
+    out = ROOT / "tests" / "cpp" / "_build"
+    out.mkdir(exist_ok=True)
+    exe = out / f"{name}_san"
+    subprocess.run(["g++", "-std=c++17", "-O0", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", *extra, str(ROOT / "tests" / "cpp" / f"{name}.cpp"),
+                    *[str(PKG / "csrc" / s) for s in sources], "-o", str(exe), "-lz", "-pthread"], check=True)
+    return exe
+
+
+def test_launch_plan_under_sanitizers():
+    """tests/cpp/test_launch_plan.cpp with csrc/launch_plan.cpp alone: a sample launch's LDS layout (LDS / global /
+    pool mode, the record caps, the top region against the upload's budget) and its chunks, at the edges."""
+    exe = _sanitized_host_program("test_launch_plan", ["launch_plan.cpp"])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "launch plan checks OK" in r.stdout
+
+
+def test_scene_image_under_sanitizers():
+    """tests/cpp/test_scene_image.cpp with csrc/scene_image.cpp, the layouts and the loader: the arrays an upload
+    sends for hand-made trees and Rubik's under every layout choice, their properties, and their bytes against
+    fingerprints of what the upload sent before that code became host-only."""
+    exe = _sanitized_host_program("test_scene_image", ["scene_image.cpp", "scene_layout.cpp", "scene.cpp"],
+                                  ["-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__"])
+    r = subprocess.run([str(exe), str(RUBIK)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "Rubik: 1188 triangles, 427 nodes" in r.stdout and "scene image checks OK (60 images pinned)" in r.stdout
