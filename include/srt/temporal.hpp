@@ -1,0 +1,63 @@
+// srt/temporal.hpp -- header-only C++ mirror of include/srt_temporal.h: srt::Temporal, RAII over the C ABI with
+// the same method names.  Errors throw std::runtime_error carrying srt_last_error().
+#pragma once
+
+#include <stdexcept>
+#include <string>
+#include <utility>
+
+#include "../srt_temporal.h"
+
+namespace srt {
+
+class Temporal {
+ public:
+  // Full frames of width x height on `device`; `stream` is a hipStream_t (nullptr: a stream of its own).
+  Temporal(int device, void* stream, int width, int height) {
+    Check(srt_temporal_create(device, stream, width, height, &t_), "srt_temporal_create");
+  }
+  ~Temporal() {
+    if (t_) srt_temporal_destroy(t_);
+  }
+  Temporal(const Temporal&) = delete;
+  Temporal& operator=(const Temporal&) = delete;
+  Temporal(Temporal&& o) noexcept : t_(std::exchange(o.t_, nullptr)) {}
+  Temporal& operator=(Temporal&& o) noexcept {
+    if (this != &o) {
+      if (t_) srt_temporal_destroy(t_);
+      t_ = std::exchange(o.t_, nullptr);
+    }
+    return *this;
+  }
+
+  srt_temporal_params params() const {
+    srt_temporal_params p{};
+    Check(srt_temporal_get_params(t_, &p), "srt_temporal_get_params");
+    return p;
+  }
+  void set_params(const srt_temporal_params& p) { Check(srt_temporal_set_params(t_, &p), "srt_temporal_set_params"); }
+  // Drops the history (after a scene or model-matrix change).
+  void reset() { Check(srt_temporal_reset(t_), "srt_temporal_reset"); }
+  // Device pointers; only enqueues on the object's stream.  out receives (colour, N).
+  void accumulate(const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev, const srt_temporal_camera& cam,
+                  void* out_rgba32f_dev) {
+    Check(srt_temporal_accumulate(t_, accum_rgba32f_dev, frames, guide_dev, &cam, out_rgba32f_dev),
+          "srt_temporal_accumulate");
+  }
+  int get_int(const char* name) const {
+    int v = 0;
+    Check(srt_temporal_get_int(t_, name, &v), name);
+    return v;
+  }
+  void* stream() const { return srt_temporal_stream(t_); }
+  srt_temporal* handle() const { return t_; }
+
+ private:
+  static void Check(int rc, const char* what) {
+    if (rc != SRT_OK)
+      throw std::runtime_error(std::string(what) + " failed with status " + std::to_string(rc) + ": " + srt_last_error());
+  }
+  srt_temporal* t_ = nullptr;
+};
+
+}  // namespace srt

@@ -1,0 +1,191 @@
+// temporal.hip -- the temporal reprojection of include/srt_temporal.h: the object, its ping-pong history and
+// the launch of temporal.hpp's kernel.  A translation unit of its own, as query.hip and denoise.hip are:
+// pathtrace.hip and its headers (the device code srt_code_hash identifies) are only read.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "../../include/srt_temporal.h"
+#include "denoise_host.hpp"
+#include "srt_internal.hpp"
+#include "temporal.hpp"
+#include "temporal_host.hpp"
+
+#define THIP_OK(expr)                                                         \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                   \
+      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
+      return SRT_ERR_HIP;                                                     \
+    }                                                                         \
+  } while (0)
+
+struct srt_temporal {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int width = 0, height = 0;
+  srt::temporal::Sizes sizes;
+  float4* d_color[2] = {nullptr, nullptr};  // rgb | N
+  float4* d_guide[2] = {nullptr, nullptr};  // normal | t
+  uint32_t* d_id[2] = {nullptr, nullptr};   // BVH record, all ones for a miss
+  srt_temporal_params params;
+  srt::temporal::History hist;
+  int last_launches = 0;
+};
+
+namespace {
+
+void FreeAll(srt_temporal* tp) {
+  for (int k = 0; k < 2; ++k) {
+    if (tp->d_color[k]) (void)hipFree(tp->d_color[k]);
+    if (tp->d_guide[k]) (void)hipFree(tp->d_guide[k]);
+    if (tp->d_id[k]) (void)hipFree(tp->d_id[k]);
+  }
+  if (tp->own_stream && tp->stream) (void)hipStreamDestroy(tp->stream);
+}
+
+int Allocate(srt_temporal* tp) {
+  THIP_OK(hipSetDevice(tp->device));
+  if (!tp->stream) {
+    THIP_OK(hipStreamCreateWithFlags(&tp->stream, hipStreamNonBlocking));
+    tp->own_stream = true;
+  }
+  for (int k = 0; k < 2; ++k) {
+    THIP_OK(hipMalloc(&tp->d_color[k], tp->sizes.color_bytes));
+    THIP_OK(hipMalloc(&tp->d_guide[k], tp->sizes.guide_bytes));
+    THIP_OK(hipMalloc(&tp->d_id[k], tp->sizes.id_bytes));
+  }
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_temporal_abi_version(void) { return SRT_TEMPORAL_ABI_VERSION; }
+
+int srt_temporal_create(int device, void* stream, int width, int height, srt_temporal** out) {
+  if (!out) return SRT_ERR_INVALID;
+  *out = nullptr;
+  srt::temporal::Sizes sizes;
+  if (int rc = srt::temporal::PlanBuffers(width, height, &sizes)) {  // before any device is touched
+    srt::SetError(rc == SRT_ERR_LIMIT ? "srt_temporal_create: image past 65535 in a dimension or 2^28 pixels"
+                                      : "srt_temporal_create: width and height must be at least 1");
+    return rc;
+  }
+  srt_temporal* tp = new srt_temporal();
+  tp->device = device;
+  tp->stream = static_cast<hipStream_t>(stream);
+  tp->width = width;
+  tp->height = height;
+  tp->sizes = sizes;
+  tp->params = srt::temporal::DefaultParams();
+  if (int rc = Allocate(tp)) {
+    FreeAll(tp);
+    delete tp;
+    return rc;
+  }
+  *out = tp;
+  return SRT_OK;
+}
+
+int srt_temporal_destroy(srt_temporal* tp) {
+  if (!tp) return SRT_ERR_INVALID;
+  (void)hipSetDevice(tp->device);
+  if (tp->stream) (void)hipStreamSynchronize(tp->stream);
+  FreeAll(tp);
+  delete tp;
+  return SRT_OK;
+}
+
+void* srt_temporal_stream(srt_temporal* tp) { return tp ? tp->stream : nullptr; }
+
+int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
+  if (!tp || !name || !v) return SRT_ERR_INVALID;
+  const std::string n(name);
+  if (n == "width") *v = tp->width;
+  else if (n == "height") *v = tp->height;
+  else if (n == "max_history") *v = (int)tp->params.max_history;
+  else if (n == "history") *v = tp->hist.valid ? 1 : 0;
+  else if (n == "frames") *v = (int)tp->hist.frames;
+  else if (n == "scratch.bytes") *v = (int)(tp->sizes.scratch_bytes < 0x7FFFFFFFu ? tp->sizes.scratch_bytes : 0x7FFFFFFFu);
+  else if (n == "launches") *v = tp->last_launches;
+  else return SRT_ERR_NOT_FOUND;
+  return SRT_OK;
+}
+
+int srt_temporal_get_params(srt_temporal* tp, srt_temporal_params* p) {
+  if (!tp || !p) return SRT_ERR_INVALID;
+  *p = tp->params;
+  return SRT_OK;
+}
+
+int srt_temporal_set_params(srt_temporal* tp, const srt_temporal_params* p) {
+  if (!tp) return SRT_ERR_INVALID;
+  if (int rc = srt::temporal::ValidateParams(p)) {
+    srt::SetError("srt_temporal_set_params: max_history 1..65535, depth_tol finite and > 0, normal_min in [-1, 1]");
+    return rc;
+  }
+  tp->params = *p;
+  return SRT_OK;
+}
+
+int srt_temporal_reset(srt_temporal* tp) {
+  if (!tp) return SRT_ERR_INVALID;
+  srt::temporal::Reset(&tp->hist);
+  return SRT_OK;
+}
+
+int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                            const srt_temporal_camera* cam, void* out_rgba32f_dev) {
+  if (!tp || !accum_rgba32f_dev || !guide_dev || !cam || !out_rgba32f_dev || frames < 1) return SRT_ERR_INVALID;
+  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u)) {
+    srt::SetError("srt_temporal_accumulate: accum, guide and out must be 16-byte aligned");
+    return SRT_ERR_INVALID;
+  }
+  if (out_rgba32f_dev == accum_rgba32f_dev || out_rgba32f_dev == (const void*)guide_dev) {
+    srt::SetError("srt_temporal_accumulate: out may not alias the inputs");
+    return SRT_ERR_INVALID;
+  }
+  THIP_OK(hipSetDevice(tp->device));
+  using namespace srt::temporal;
+  TParams kp;
+  std::memset(&kp, 0, sizeof kp);
+  const int rd = tp->hist.read, wr = WriteIndex(tp->hist);
+  kp.accum = static_cast<const float4*>(accum_rgba32f_dev);
+  kp.hits = reinterpret_cast<const uint4*>(guide_dev);
+  kp.pcol = tp->d_color[rd];
+  kp.pgd = tp->d_guide[rd];
+  kp.pid = tp->d_id[rd];
+  kp.ncol = tp->d_color[wr];
+  kp.ngd = tp->d_guide[wr];
+  kp.nid = tp->d_id[wr];
+  kp.out = static_cast<float4*>(out_rgba32f_dev);
+  kp.W = tp->width;
+  kp.H = tp->height;
+  kp.has_prev = tp->hist.valid ? 1 : 0;
+  kp.frames = (float)frames;
+  kp.max_history = (float)tp->params.max_history;
+  kp.depth_tol = tp->params.depth_tol;
+  kp.normal_min = tp->params.normal_min;
+  srt::denoise::Basis b;
+  srt::denoise::PrimaryBasis(cam->origin, cam->front, cam->right, cam->up, tp->width, tp->height, &b);
+  std::memcpy(kp.o, b.o, sizeof kp.o);
+  std::memcpy(kp.p00, b.p00, sizeof kp.p00);
+  std::memcpy(kp.du, b.du, sizeof kp.du);
+  std::memcpy(kp.dv, b.dv, sizeof kp.dv);
+  const srt_temporal_camera& pc = tp->hist.prev;
+  std::memcpy(kp.po, pc.origin, sizeof kp.po);
+  std::memcpy(kp.pf, pc.front, sizeof kp.pf);
+  std::memcpy(kp.pr, pc.right, sizeof kp.pr);
+  std::memcpy(kp.pu, pc.up, sizeof kp.pu);
+  hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream, kp);
+  THIP_OK(hipGetLastError());
+  Advance(&tp->hist, *cam);
+  tp->last_launches = 1;
+  return SRT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,144 @@
+// temporal.hpp -- the kernel of the temporal reprojection (include/srt_temporal.h; DESIGN.md section 5,
+// "Temporal reprojection").
+//
+// One launch per frame.  A pixel reads its accumulation sum (16 B) and its srt_hit (two 16-B words), finds
+// where its surface point lay in the previous frame and gathers the 2 x 2 history pixels around that position:
+// per tap the colour | N and the normal | t as 16-B words and the id (the hit's BVH record, all ones for a
+// miss) as 4 B.  A wave covers 64 contiguous pixels of a row, so the taps of neighbouring lanes are mostly
+// neighbouring addresses and nothing is staged in LDS.  The four taps are loaded from addresses clamped into
+// the image before any of them is tested, so the twelve loads are in flight together; a clamped tap is
+// rejected by its `inside` flag.  A pure gather: no atomics, and it writes the other set of the ping-pong
+// history than the one it reads.
+// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "temporal_host.hpp"
+
+namespace srt {
+namespace temporal {
+
+constexpr uint32_t kMissId = 0xFFFFFFFFu;
+
+struct TParams {
+  const float4* accum;   // the accumulation image (sum | 1)
+  const uint4* hits;     // the srt_hit records, 2 uint4 each
+  const float4* pcol;    // previous frame: colour | N
+  const float4* pgd;     //                 normal | t
+  const uint32_t* pid;   //                 id
+  float4* ncol;          // this frame's, for the next call
+  float4* ngd;
+  uint32_t* nid;
+  float4* out;           // (colour, N)
+  int W, H;
+  int has_prev;          // 0: no previous frame, every pixel takes (C, 1)
+  float frames;          // float(frames)
+  float max_history, depth_tol, normal_min;
+  float o[3], p00[3], du[3], dv[3];   // the current camera's pixel-centre basis (denoise_host.hpp PrimaryBasis)
+  float po[3], pf[3], pr[3], pu[3];   // the previous camera: origin, front, right, up
+};
+
+__device__ __forceinline__ bool finite1(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+  return (ax * bx + ay * by) + az * bz;
+}
+
+// A whole 16-B word in one dwordx4: the empty asm makes all four components live, or the compiler splits the
+// load at the component that is tested first (denoise.hpp has the same).
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld16(const float4* p) {
+  v4f v = *reinterpret_cast<const v4f*>(p);
+  asm("" : "+v"(v));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ uint4 ld16(const uint4* p) {
+  v4u v = *reinterpret_cast<const v4u*>(p);
+  asm("" : "+v"(v));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp) {
+  const int i = (int)blockIdx.x * kRowW + ((int)threadIdx.x & (kRowW - 1));
+  const int j = (int)blockIdx.y * kRowH + (int)threadIdx.x / kRowW;
+  if (i >= tp.W || j >= tp.H) return;
+  const int pi = j * tp.W + i;
+  const float4 acc = ld16(tp.accum + pi);
+  const uint4 h0 = ld16(tp.hits + 2 * (size_t)pi), h1 = ld16(tp.hits + 2 * (size_t)pi + 1);  // triangle t n.x n.y | n.z material bvh pad
+  const float cx = acc.x / tp.frames, cy = acc.y / tp.frames, cz = acc.z / tp.frames;
+  const uint32_t id = h0.x == kMissId ? kMissId : h1.z;
+  const float t = __uint_as_float(h0.y);
+  const float nx = __uint_as_float(h0.z), ny = __uint_as_float(h0.w), nz = __uint_as_float(h1.x);
+  float4 res = make_float4(cx, cy, cz, 1.0f);
+  if (tp.has_prev && id != kMissId) {
+    const float fi = (float)i, fj = (float)j;
+    const float dx = ((tp.p00[0] + fi * tp.du[0]) + fj * tp.dv[0]) - tp.o[0];
+    const float dy = ((tp.p00[1] + fi * tp.du[1]) + fj * tp.dv[1]) - tp.o[1];
+    const float dz = ((tp.p00[2] + fi * tp.du[2]) + fj * tp.dv[2]) - tp.o[2];
+    const float vx = (t * dx + tp.o[0]) - tp.po[0];
+    const float vy = (t * dy + tp.o[1]) - tp.po[1];
+    const float vz = (t * dz + tp.o[2]) - tp.po[2];
+    const float a = dot3(vx, vy, vz, tp.pf[0], tp.pf[1], tp.pf[2]) / dot3(tp.pf[0], tp.pf[1], tp.pf[2], tp.pf[0], tp.pf[1], tp.pf[2]);
+    const float b = dot3(vx, vy, vz, tp.pr[0], tp.pr[1], tp.pr[2]) / dot3(tp.pr[0], tp.pr[1], tp.pr[2], tp.pr[0], tp.pr[1], tp.pr[2]);
+    const float c = dot3(vx, vy, vz, tp.pu[0], tp.pu[1], tp.pu[2]) / dot3(tp.pu[0], tp.pu[1], tp.pu[2], tp.pu[0], tp.pu[1], tp.pu[2]);
+    if (a > 0.0f) {
+      const float Wf = (float)tp.W, Hf = (float)tp.H;
+      const float uu = (b / a + 0.5f) * Wf - 0.5f, vv = (c / a + 0.5f) * Hf - 0.5f;
+      if (uu >= -1.0f && uu < Wf && vv >= -1.0f && vv < Hf) {  // NaN fails; only now to integers
+        const float fu = __builtin_floorf(uu), fv = __builtin_floorf(vv);
+        const int i0 = (int)fu, j0 = (int)fv;  // -1 .. W-1, -1 .. H-1
+        const float fx = uu - fu, fy = vv - fv;
+        // all twelve loads first, from addresses clamped into the image
+        float4 qc[4], qg[4];
+        uint32_t qid[4];
+        bool inside[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int qx = i0 + (k & 1), qy = j0 + (k >> 1);
+          inside[k] = qx >= 0 && qx < tp.W && qy >= 0 && qy < tp.H;
+          const int qxc = qx < 0 ? 0 : (qx >= tp.W ? tp.W - 1 : qx), qyc = qy < 0 ? 0 : (qy >= tp.H ? tp.H - 1 : qy);
+          const int qi = qyc * tp.W + qxc;
+          qid[k] = tp.pid[qi];
+          qg[k] = ld16(tp.pgd + qi);
+          qc[k] = ld16(tp.pcol + qi);
+        }
+        float sw = 0.0f, smx = 0.0f, smy = 0.0f, smz = 0.0f, Nh = __builtin_inff();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // dy outer, dx inner
+          const float wb = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+          const float4 g = qg[k], q = qc[k];
+          bool ok = inside[k] && qid[k] == id;
+          ok = ok && dot3(nx, ny, nz, g.x, g.y, g.z) >= tp.normal_min;
+          ok = ok && __builtin_fabsf(a - g.w) <= tp.depth_tol * (a + g.w);
+          ok = ok && finite1(q.x) && finite1(q.y) && finite1(q.z) && wb > 0.0f;
+          if (ok) {
+            sw += wb;
+            smx += wb * q.x;
+            smy += wb * q.y;
+            smz += wb * q.z;
+            Nh = q.w < Nh ? q.w : Nh;
+          }
+        }
+        if (sw > 0.0f) {
+          const float hx = smx / sw, hy = smy / sw, hz = smz / sw;
+          if (finite1(cx) && finite1(cy) && finite1(cz)) {
+            const float n1 = Nh + 1.0f;
+            const float N = n1 < tp.max_history ? n1 : tp.max_history;
+            const float k = 1.0f / N;
+            res = make_float4(hx + k * (cx - hx), hy + k * (cy - hy), hz + k * (cz - hz), N);
+          } else {
+            res = make_float4(hx, hy, hz, Nh);  // a NaN sample: repaired from the history, not counted
+          }
+        }
+      }
+    }
+  }
+  tp.out[pi] = res;
+  tp.ncol[pi] = res;
+  tp.ngd[pi] = make_float4(nx, ny, nz, t);
+  tp.nid[pi] = id;
+}
+
+}  // namespace temporal
+}  // namespace srt

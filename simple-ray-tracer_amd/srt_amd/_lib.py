@@ -223,6 +223,31 @@ _DENOISE_SIGS = {
 }
 DENOISE_SYMBOLS = tuple(_DENOISE_SIGS)
 
+
+class TemporalParams(C.Structure):
+    """srt_temporal_params (include/srt_temporal.h)."""
+    _fields_ = [("max_history", C.c_uint32), ("depth_tol", C.c_float), ("normal_min", C.c_float)]
+
+
+class TemporalCamera(C.Structure):
+    """srt_temporal_camera (include/srt_temporal.h)."""
+    _fields_ = [("origin", C.c_float * 3), ("front", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3)]
+
+
+# include/srt_temporal.h: the temporal reprojection (its own header and version)
+_TEMPORAL_SIGS = {
+    "srt_temporal_abi_version": (C.c_int, []),
+    "srt_temporal_create": (C.c_int, [C.c_int, P, C.c_int, C.c_int, C.POINTER(P)]),
+    "srt_temporal_destroy": (C.c_int, [P]),
+    "srt_temporal_stream": (P, [P]),
+    "srt_temporal_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_temporal_get_params": (C.c_int, [P, C.POINTER(TemporalParams)]),
+    "srt_temporal_set_params": (C.c_int, [P, C.POINTER(TemporalParams)]),
+    "srt_temporal_reset": (C.c_int, [P]),
+    "srt_temporal_accumulate": (C.c_int, [P, P, C.c_int, P, C.POINTER(TemporalCamera), P]),
+}
+TEMPORAL_SYMBOLS = tuple(_TEMPORAL_SIGS)
+
 _lib = None
 
 
@@ -254,7 +279,7 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()):
+        for name, (res, args) in list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Time of the temporal reprojection (include/srt_temporal.h) on a rendered Rubik frame at WIDTH x HEIGHT.
+
+It times srt_temporal_accumulate by torch.cuda.Event pairs around the enqueued call (--warmup runs unmeasured,
+median of --reps), in three states: without history (the first call after a reset: no taps), with the history of
+the same camera (every hit pixel gathers its four taps), and with the history of a camera one small step away
+(the interactive case: most hit pixels gather, the taps are no longer aligned with the lanes).  Beside them, timed
+the same way in the same process: a float4 copy of one frame (the bandwidth floor) and one a-trous pass of the
+denoiser (srt_denoise_run with passes = 1), which the call is to be read against.
+Nothing is asserted: this is a measurement tool.  --out writes the JSON document (profiles/temporal.json).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import pathlib
+import statistics
+import sys
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+for p in (str(ROOT / "simple-ray-tracer_amd"), str(ROOT)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def time_calls(torch, fn, warmup, reps, before=None):
+    """Median, min and max ms of `fn` over `reps` runs; `before` (untimed) is enqueued ahead of each."""
+    for _ in range(warmup):
+        if before:
+            before()
+        fn()
+    torch.cuda.current_stream().synchronize()
+    ms = []
+    for _ in range(reps):
+        if before:
+            before()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return round(statistics.median(ms), 4), round(min(ms), 4), round(max(ms), 4)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=1)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out", help="write the results to this JSON file")
+    a = ap.parse_args()
+    if a.warmup < 3 or a.reps < 10:
+        ap.error("at least 3 warm-up runs and 10 measured ones")
+    import torch
+
+    from srt_amd import _lib
+    from srt_amd import render as R
+    from srt_amd.denoise import Denoiser
+    from srt_amd.query import Query
+    from srt_amd.temporal import Temporal, _camera
+
+    W, H = a.width, a.height
+    setup = R.make_setup(W, H, show_model=True, models=[R.rubik_model(ROOT / "tests" / "golden" / "objects")])
+    rdr = R.Renderer(setup)
+    lib = _lib.lib()
+    doc = {"tool": "tools/bench_temporal.py", "width": W, "height": H, "spp": a.spp, "scene": "rubik",
+           "device": torch.cuda.get_device_name(0), "code_hash": lib.srt_code_hash().decode(),
+           "warmup": a.warmup, "reps": a.reps,
+           "timing": "torch.cuda.Event pairs around the enqueued call on one stream; median [min, max] ms; the "
+                     "calls that set a state up (reset, the previous frame) are enqueued before the first event"}
+    try:
+        rdr.render(a.spp)
+        rdr.finish()
+        frames = rdr.accum_frames
+        acc_ptr, _ = rdr.compute.image_pointers()
+        stream = torch.cuda.Stream()
+        with torch.cuda.stream(stream):
+            out = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
+            src = torch.rand((H, W, 4), dtype=torch.float32, device="cuda")
+            doc["copy_float4_frame_ms"] = time_calls(torch, lambda: out.copy_(src), a.warmup, a.reps)
+            doc["frame_bytes"] = W * H * 16
+            with Query(setup.scene, stream=stream) as q, Denoiser(W, H, stream=stream) as dn, \
+                    Temporal(W, H, stream=stream) as tp:
+                q.set_bvh_count(setup.bvh_count)
+                cam0 = _camera(setup.camera)
+                hits0 = q.closest(dn.primary_rays(setup.camera))
+                setup.camera.MoveRight(0.5)
+                setup.camera.Rotate(-1.0, 0.0)
+                cam1 = _camera(setup.camera)
+                hits1 = q.closest(dn.primary_rays(setup.camera))
+                doc["hit_fraction"] = round(float(hits0.hit.float().mean()), 4)
+                doc["scratch_bytes"] = tp.get_int("scratch.bytes")
+                # bytes a call must move per pixel: accum 16 + srt_hit 32 read; out 16 + history 16 + 16 + 4 written;
+                # a hit pixel with history also gathers 4 x 36 B, mostly shared with its neighbours through the caches
+                doc["bytes_min_per_pixel"] = 100
+
+                def call(hits, cam):
+                    return lib.srt_temporal_accumulate(tp.handle, C.c_void_p(acc_ptr), frames, C.c_void_p(hits.raw.data_ptr()),
+                                                       C.byref(cam), C.c_void_p(out.data_ptr()))
+
+                doc["accumulate_no_history_ms"] = time_calls(torch, lambda: call(hits0, cam0), a.warmup, a.reps,
+                                                             before=lambda: lib.srt_temporal_reset(tp.handle))
+                doc["accumulate_same_camera_ms"] = time_calls(torch, lambda: call(hits0, cam0), a.warmup, a.reps)
+                doc["accumulate_moved_camera_ms"] = time_calls(torch, lambda: call(hits1, cam1), a.warmup, a.reps,
+                                                               before=lambda: call(hits0, cam0))
+                tp.synchronize()
+                n = out[..., 3]
+                doc["moved_camera_reuse_fraction_of_hits"] = round(float((n[hits1.hit.reshape(H, W)] >= 2).float().mean()), 4)
+                dn.set_params(passes=1)
+                out2 = torch.empty_like(out)
+                doc["atrous_one_pass_ms"] = time_calls(
+                    torch, lambda: lib.srt_denoise_run(dn.handle, C.c_void_p(acc_ptr), frames, C.c_void_p(hits0.raw.data_ptr()),
+                                                       C.c_void_p(out2.data_ptr()), None), a.warmup, a.reps)
+                # the same three once more: the first series of a process reads slow ("Denoiser")
+                doc["second_series"] = {
+                    "copy_float4_frame_ms": time_calls(torch, lambda: out2.copy_(src), a.warmup, a.reps),
+                    "accumulate_same_camera_ms": time_calls(torch, lambda: call(hits0, cam0), a.warmup, a.reps),
+                    "accumulate_moved_camera_ms": time_calls(torch, lambda: call(hits1, cam1), a.warmup, a.reps,
+                                                             before=lambda: call(hits0, cam0)),
+                }
+        m = doc["second_series"]["accumulate_moved_camera_ms"][0]
+        doc["moved_over_copy"] = round(m / doc["second_series"]["copy_float4_frame_ms"][0], 2)
+        doc["moved_over_atrous_pass"] = round(m / doc["atrous_one_pass_ms"][0], 2)
+        doc["moved_min_bytes_GBps"] = round(W * H * doc["bytes_min_per_pixel"] / (m * 1e-3) / 1e9, 1)
+    finally:
+        rdr.close()
+    print(json.dumps(doc), flush=True)
+    if a.out:
+        pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(a.out).write_text(json.dumps(doc, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

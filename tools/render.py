@@ -1,7 +1,7 @@
 """Render a scene to an image file on the GPU: the reference's progressive loop, headless.
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
-                              [--max-depth D] [--out frame.png] [--denoise]
+                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -28,7 +28,16 @@ def main():
     ap.add_argument("--denoise", action="store_true",
                     help="also write <out>_denoised.<ext>: the frame through the edge-avoiding filter, guided by a "
                          "closest-hit query of the pixel-centre rays (mesh scenes; sphere pixels pass unfiltered)")
+    ap.add_argument("--orbit", type=int, default=0, metavar="K",
+                    help="mesh scenes: render K frames of --spp each along a small fixed camera path, resetting the "
+                         "accumulation per frame as the frame loop does while the camera moves, and write the last "
+                         "frame three ways: <out> (raw), <out>_denoised and <out>_temporal (accumulated over the path "
+                         "by temporal reprojection, then denoised)")
     a = ap.parse_args()
+    if a.orbit and a.scene == "spheres":
+        ap.error("--orbit needs a mesh scene: the guide is a ray query")
+    if a.orbit < 0:
+        ap.error("--orbit K: K >= 1")
     if a.scene == "rubik":
         models, show = [R.rubik_model(ROOT / "tests" / "golden" / "objects")], True
     elif a.scene == "synthetic":
@@ -44,6 +53,17 @@ def main():
         models, show = None, False
     setup = R.make_setup(a.width, a.height, show_model=show, models=models, max_depth=a.max_depth)
     r = R.Renderer(setup)
+    if a.orbit:
+        try:
+            t0 = time.perf_counter()
+            paths = orbit(r, setup, a.orbit, a.spp, a.out)
+            dt = time.perf_counter() - t0
+        finally:
+            r.close()
+        print(f"{a.orbit} frames of {a.width}x{a.height} @ {a.spp} spp in {dt:.3f} s; the last one:")
+        for what, p in zip(("raw", "denoised", "temporal + denoised"), paths):
+            print(f"{p}: {what}")
+        return
     try:
         t0 = time.perf_counter()
         r.render(a.spp)
@@ -81,6 +101,45 @@ def denoise(r, setup, out):
         dn.synchronize()
         S.write_image(path, rgba8.cpu().numpy())
     return path
+
+
+ORBIT_STEP = (0.5, -1.0)  # per frame: MoveRight(0.5), then Rotate(-1 degree of yaw, 0): the camera circles the model
+
+
+def orbit(r, setup, frames, spp, out):
+    """`frames` frames of `spp` samples along ORBIT_STEP, each after a reset of the accumulation; every frame goes
+    through srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame
+    raw, denoised, and temporally accumulated then denoised; returns the three paths."""
+    import srt_amd as S
+    from srt_amd.denoise import Denoiser
+    from srt_amd.query import Query
+    from srt_amd.temporal import Temporal
+
+    out = pathlib.Path(out)
+    paths = [out] + [out.with_name(out.stem + s + out.suffix) for s in ("_denoised", "_temporal")]
+    cam, c = setup.camera, r.compute
+    acc_ptr, _ = c.image_pointers()
+    with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, Query(setup.scene) as q:
+        q.set_bvh_count(setup.bvh_count)
+        for k in range(frames):
+            if k:
+                cam.MoveRight(ORBIT_STEP[0])
+                cam.Rotate(ORBIT_STEP[1], 0.0)
+                c.SetVec3("cameraOrigin", cam.getOrigin())
+                c.SetVec3("cameraDirection", cam.getForward())
+                c.SetVec3("cameraUp", cam.getUpVector())
+                c.SetVec3("cameraRight", cam.getRightVector())
+            r.render(spp)  # clears first: the frame loop resets on any input
+            r.finish()
+            hits = q.closest(dn.primary_rays(cam))
+            acc = tp.accumulate(acc_ptr, r.accum_frames, hits, cam)
+        c.save_image(paths[0])
+        _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
+        _, rgba8_t = dn.run(acc, 1, hits, srgb=True)
+        dn.synchronize()
+        S.write_image(paths[1], rgba8.cpu().numpy())
+        S.write_image(paths[2], rgba8_t.cpu().numpy())
+    return paths
 
 
 if __name__ == "__main__":
