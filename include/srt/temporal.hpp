@@ -1,5 +1,5 @@
-// srt/temporal.hpp -- header-only C++ mirror of include/srt_temporal.h: srt::Temporal, RAII over the C ABI with
-// the same method names.  Errors throw std::runtime_error carrying srt_last_error().
+// srt/temporal.hpp -- header-only C++ mirror of include/srt_temporal.h and include/srt_temporal_motion.h:
+// srt::Temporal, RAII over the C ABI with the same method names.  Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
 #include <stdexcept>
@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../srt_temporal.h"
+#include "../srt_temporal_motion.h"
 
 namespace srt {
 
@@ -36,7 +37,17 @@ class Temporal {
     return p;
   }
   void set_params(const srt_temporal_params& p) { Check(srt_temporal_set_params(t_, &p), "srt_temporal_set_params"); }
-  // Drops the history (after a scene or model-matrix change).
+  // The pose of BVH records 0..n-1 from now on (srt_temporal_motion.h); n == 0: the static behaviour.
+  void SetModels(const srt_temporal_model* models, uint32_t n) {
+    Check(srt_temporal_set_models(t_, models, n), "srt_temporal_set_models");
+  }
+  // world_to_model = frame and its affine inverse.
+  static srt_temporal_model ModelFromFrame(const float frame[16]) {
+    srt_temporal_model m{};
+    Check(srt_temporal_model_from_frame(frame, &m), "srt_temporal_model_from_frame");
+    return m;
+  }
+  // Drops the history (after a scene change, or a model-matrix change that SetModels was not told of).
   void reset() { Check(srt_temporal_reset(t_), "srt_temporal_reset"); }
   // Device pointers; only enqueues on the object's stream.  out receives (colour, N).
   void accumulate(const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev, const srt_temporal_camera& cam,

@@ -35,7 +35,8 @@
  * The history assumes a STATIC scene: the caller resets after a scene or model-matrix change.  Only FULL
  * frames are supported (row pitch = width, row 0 at the bottom, index j*W + i), as in srt_denoise.h.  Out of
  * scope: moving geometry and motion vectors, variance estimates, sky (miss) reprojection, band-tiled or
- * multi-GPU frames, sphere scenes.
+ * multi-GPU frames, sphere scenes.  Models that move between frames: srt_temporal_motion.h, which adds to this
+ * header and leaves it as it is.
  *
  * Additive to srt_amd.h, srt_query.h and srt_denoise.h (their versions are unchanged); versioned on its own.
  */

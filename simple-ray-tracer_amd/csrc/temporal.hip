@@ -1,5 +1,5 @@
-// temporal.hip -- the temporal reprojection of include/srt_temporal.h: the object, its ping-pong history and
-// the launch of temporal.hpp's kernel.  A translation unit of its own, as query.hip and denoise.hip are:
+// temporal.hip -- the temporal reprojection of include/srt_temporal.h and include/srt_temporal_motion.h: the
+// object, its ping-pong history, the poses' device array and the launches of temporal.hpp's kernels.  A translation unit of its own, as query.hip and denoise.hip are:
 // pathtrace.hip and its headers (the device code srt_code_hash identifies) are only read.
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/srt_temporal.h"
+#include "../../include/srt_temporal_motion.h"
 #include "denoise_host.hpp"
 #include "srt_internal.hpp"
 #include "temporal.hpp"
@@ -32,6 +33,9 @@ struct srt_temporal {
   uint32_t* d_id[2] = {nullptr, nullptr};   // BVH record, all ones for a miss
   srt_temporal_params params;
   srt::temporal::History hist;
+  srt::temporal::Poses poses;
+  uint4* d_motion = nullptr;      // one MotionRecord per BVH record; grown by srt_temporal_set_models only
+  uint32_t motion_capacity = 0;   // records
   int last_launches = 0;
 };
 
@@ -43,6 +47,7 @@ void FreeAll(srt_temporal* tp) {
     if (tp->d_guide[k]) (void)hipFree(tp->d_guide[k]);
     if (tp->d_id[k]) (void)hipFree(tp->d_id[k]);
   }
+  if (tp->d_motion) (void)hipFree(tp->d_motion);
   if (tp->own_stream && tp->stream) (void)hipStreamDestroy(tp->stream);
 }
 
@@ -112,6 +117,8 @@ int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
   else if (n == "frames") *v = (int)tp->hist.frames;
   else if (n == "scratch.bytes") *v = (int)(tp->sizes.scratch_bytes < 0x7FFFFFFFu ? tp->sizes.scratch_bytes : 0x7FFFFFFFu);
   else if (n == "launches") *v = tp->last_launches;
+  else if (n == "models") *v = (int)tp->poses.cur.size();
+  else if (n == "models.bytes") *v = (int)(tp->motion_capacity * sizeof(srt::temporal::MotionRecord));
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -135,6 +142,7 @@ int srt_temporal_set_params(srt_temporal* tp, const srt_temporal_params* p) {
 int srt_temporal_reset(srt_temporal* tp) {
   if (!tp) return SRT_ERR_INVALID;
   srt::temporal::Reset(&tp->hist);
+  srt::temporal::ResetPoses(&tp->poses);
   return SRT_OK;
 }
 
@@ -181,10 +189,58 @@ int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int
   std::memcpy(kp.pf, pc.front, sizeof kp.pf);
   std::memcpy(kp.pr, pc.right, sizeof kp.pr);
   std::memcpy(kp.pu, pc.up, sizeof kp.pu);
-  hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream, kp);
+  const uint32_t n = (uint32_t)tp->poses.cur.size();  // <= motion_capacity: srt_temporal_set_models grew the array
+  if (n == 0) {
+    hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream, kp);
+  } else {
+    // The records travel in kernel arguments, which the launch copies before it returns; stream order puts them
+    // behind the previous frame's kernel, so one device array serves.
+    MotionChunk chunk;
+    for (uint32_t first = 0; first < n; first += kUploadChunk) {
+      const uint32_t count = FillChunk(tp->poses, first, &chunk);
+      hipLaunchKernelGGL(temporal_motion_upload_kernel, dim3(1), dim3(kUploadLanes), 0, tp->stream, chunk, tp->d_motion, first, count);
+    }
+    hipLaunchKernelGGL(temporal_accumulate_motion_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream,
+                       kp, (const uint4*)tp->d_motion, n);
+  }
   THIP_OK(hipGetLastError());
   Advance(&tp->hist, *cam);
-  tp->last_launches = 1;
+  AdvancePoses(&tp->poses);
+  tp->last_launches = 1 + (int)UploadLaunches(n);
+  return SRT_OK;
+}
+
+int srt_temporal_motion_abi_version(void) { return SRT_TEMPORAL_MOTION_ABI_VERSION; }
+
+int srt_temporal_set_models(srt_temporal* tp, const srt_temporal_model* models, uint32_t n) {
+  if (int rc = srt::temporal::ValidateModels(models, n)) {  // before the object or any device is touched
+    srt::SetError(rc == SRT_ERR_LIMIT ? "srt_temporal_set_models: more than 65535 records"
+                                      : "srt_temporal_set_models: every entry finite and each bottom row (0, 0, 0, 1)");
+    return rc;
+  }
+  if (!tp) {
+    srt::SetError("srt_temporal_set_models: NULL object");
+    return SRT_ERR_INVALID;
+  }
+  if (n > tp->motion_capacity) {
+    THIP_OK(hipSetDevice(tp->device));
+    uint4* grown = nullptr;
+    THIP_OK(hipMalloc(&grown, (size_t)n * sizeof(srt::temporal::MotionRecord)));
+    if (tp->d_motion) {
+      (void)hipStreamSynchronize(tp->stream);  // an enqueued frame may still read the old array
+      (void)hipFree(tp->d_motion);
+    }
+    tp->d_motion = grown;
+    tp->motion_capacity = n;
+  }
+  return srt::temporal::SetModels(&tp->poses, models, n);
+}
+
+int srt_temporal_model_from_frame(const float frame[16], srt_temporal_model* out) {
+  if (int rc = srt::temporal::ModelFromFrame(frame, out)) {
+    srt::SetError("srt_temporal_model_from_frame: a finite, affine, non-singular frame");
+    return rc;
+  }
   return SRT_OK;
 }
 

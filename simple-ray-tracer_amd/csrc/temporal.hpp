@@ -10,6 +10,13 @@
 // rejected by its `inside` flag.  A pure gather: no atomics, and it writes the other set of the ping-pong
 // history than the one it reads.
 // The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division).
+//
+// Moving models (include/srt_temporal_motion.h): the body is a template with two kernels over it.
+// temporal_accumulate_kernel is the static instance, the code an object without poses has always run.
+// temporal_accumulate_motion_kernel also reads the hit record's 64-B MotionRecord (four 16-B words, one address
+// per lane, mostly the same one across a wave) ahead of the taps and moves the surface point by M_r when the
+// record is flagged MOVING.  temporal_motion_upload_kernel writes a chunk of those records, which it receives
+// by value in its kernel arguments, with ordinary vector stores.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -59,7 +66,8 @@ __device__ __forceinline__ uint4 ld16(const uint4* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-__global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp) {
+template <bool MOTION>
+__device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* __restrict__ motion, uint32_t n_motion) {
   const int i = (int)blockIdx.x * kRowW + ((int)threadIdx.x & (kRowW - 1));
   const int j = (int)blockIdx.y * kRowH + (int)threadIdx.x / kRowW;
   if (i >= tp.W || j >= tp.H) return;
@@ -76,9 +84,31 @@ __global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp)
     const float dx = ((tp.p00[0] + fi * tp.du[0]) + fj * tp.dv[0]) - tp.o[0];
     const float dy = ((tp.p00[1] + fi * tp.du[1]) + fj * tp.dv[1]) - tp.o[1];
     const float dz = ((tp.p00[2] + fi * tp.du[2]) + fj * tp.dv[2]) - tp.o[2];
-    const float vx = (t * dx + tp.o[0]) - tp.po[0];
-    const float vy = (t * dy + tp.o[1]) - tp.po[1];
-    const float vz = (t * dz + tp.o[2]) - tp.po[2];
+    float vx, vy, vz;
+    if constexpr (MOTION) {
+      float x = t * dx + tp.o[0], y = t * dy + tp.o[1], z = t * dz + tp.o[2];
+      // id is a hit's record here (the miss id was tested above); a record past the poses is STATIC
+      const bool posed = id < n_motion;
+      // One address per lane, whole 16-B words.  Fetching the record once per wave when its lanes share it (a
+      // compare against the first lane's id) was measured and is no faster ("Moving models").
+      const uint4* rec = motion + 4 * (size_t)(posed ? id : 0u);
+      const uint4 r0 = ld16(rec), r1 = ld16(rec + 1), r2 = ld16(rec + 2), r3 = ld16(rec + 3);
+      if (posed && r3.x != 0u) {  // MOVING: x' = M_r x, each row as traversal.hpp's xform orders it
+        const float mx = ((__uint_as_float(r0.x) * x + __uint_as_float(r0.y) * y) + __uint_as_float(r0.z) * z) + __uint_as_float(r0.w);
+        const float my = ((__uint_as_float(r1.x) * x + __uint_as_float(r1.y) * y) + __uint_as_float(r1.z) * z) + __uint_as_float(r1.w);
+        const float mz = ((__uint_as_float(r2.x) * x + __uint_as_float(r2.y) * y) + __uint_as_float(r2.z) * z) + __uint_as_float(r2.w);
+        x = mx;
+        y = my;
+        z = mz;
+      }
+      vx = x - tp.po[0];
+      vy = y - tp.po[1];
+      vz = z - tp.po[2];
+    } else {
+      vx = (t * dx + tp.o[0]) - tp.po[0];
+      vy = (t * dy + tp.o[1]) - tp.po[1];
+      vz = (t * dz + tp.o[2]) - tp.po[2];
+    }
     const float a = dot3(vx, vy, vz, tp.pf[0], tp.pf[1], tp.pf[2]) / dot3(tp.pf[0], tp.pf[1], tp.pf[2], tp.pf[0], tp.pf[1], tp.pf[2]);
     const float b = dot3(vx, vy, vz, tp.pr[0], tp.pr[1], tp.pr[2]) / dot3(tp.pr[0], tp.pr[1], tp.pr[2], tp.pr[0], tp.pr[1], tp.pr[2]);
     const float c = dot3(vx, vy, vz, tp.pu[0], tp.pu[1], tp.pu[2]) / dot3(tp.pu[0], tp.pu[1], tp.pu[2], tp.pu[0], tp.pu[1], tp.pu[2]);
@@ -138,6 +168,31 @@ __global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp)
   tp.ncol[pi] = res;
   tp.ngd[pi] = make_float4(nx, ny, nz, t);
   tp.nid[pi] = id;
+}
+
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp) {
+  accumulate_pixel<false>(tp, nullptr, 0u);
+}
+
+// `motion`: n_motion >= 1 MotionRecords, 64-B aligned.
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_motion_kernel(TParams tp, const uint4* __restrict__ motion,
+                                                                            uint32_t n_motion) {
+  accumulate_pixel<true>(tp, motion, n_motion);
+}
+
+// One block of kUploadLanes lanes: lane k stores 16-B word k of the chunk, records [first, first + count) of `dst`
+// (count <= kUploadChunk; the host has checked first + count against the array's capacity).
+constexpr int kUploadLanes = (int)kUploadChunk * 4;
+__global__ __launch_bounds__(kUploadLanes) void temporal_motion_upload_kernel(MotionChunk chunk, uint4* __restrict__ dst,
+                                                                              uint32_t first, uint32_t count) {
+  const uint32_t k = threadIdx.x;
+  if (k >= count * 4u) return;
+  const MotionRecord& r = chunk.r[k >> 2];
+  const uint32_t w = k & 3u;
+  const float* m = r.m + 4 * (w < 3u ? w : 0u);
+  const uint4 v = w < 3u ? make_uint4(__float_as_uint(m[0]), __float_as_uint(m[1]), __float_as_uint(m[2]), __float_as_uint(m[3]))
+                         : make_uint4(r.moving, 0u, 0u, 0u);
+  dst[4 * (size_t)first + k] = v;
 }
 
 }  // namespace temporal

@@ -2,6 +2,7 @@
 #include "temporal_host.hpp"
 
 #include <cmath>
+#include <cstring>
 
 namespace srt {
 namespace temporal {
@@ -48,6 +49,104 @@ void Advance(History* h, const srt_temporal_camera& cam) {
   h->valid = true;
   h->prev = cam;
   if (h->frames < 0x7FFFFFFFu) ++h->frames;
+}
+
+// ---- moving models ----
+
+namespace {
+
+bool AffineFinite(const float m[16]) {
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(m[k])) return false;
+  return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f;
+}
+
+}  // namespace
+
+int ValidateModels(const srt_temporal_model* models, uint32_t n) {
+  if (n > kMaxModels) return SRT_ERR_LIMIT;
+  if (n && !models) return SRT_ERR_INVALID;
+  for (uint32_t r = 0; r < n; ++r)
+    if (!AffineFinite(models[r].world_to_model) || !AffineFinite(models[r].model_to_world)) return SRT_ERR_INVALID;
+  return SRT_OK;
+}
+
+int ModelFromFrame(const float frame[16], srt_temporal_model* out) {
+  if (!frame || !out || !AffineFinite(frame)) return SRT_ERR_INVALID;
+  // element (row i, column k) of the column-major frame
+  double a[3][3], t[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int k = 0; k < 3; ++k) a[i][k] = (double)frame[4 * k + i];
+    t[i] = (double)frame[12 + i];
+  }
+  double c[3][3];  // cofactors: the inverse is their transpose over the determinant
+  for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 3; ++k) {
+      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+      c[i][k] = a[i1][k1] * a[i2][k2] - a[i1][k2] * a[i2][k1];
+    }
+  const double det = a[0][0] * c[0][0] + a[0][1] * c[0][1] + a[0][2] * c[0][2];
+  if (!(det != 0.0) || !std::isfinite(det)) return SRT_ERR_INVALID;
+  float inv[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+  for (int i = 0; i < 3; ++i) {
+    double ti = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const double e = c[k][i] / det;
+      inv[4 * k + i] = (float)e;
+      ti -= e * t[k];
+    }
+    inv[12 + i] = (float)ti;
+  }
+  if (!AffineFinite(inv)) return SRT_ERR_INVALID;
+  std::memcpy(out->world_to_model, frame, sizeof out->world_to_model);
+  std::memcpy(out->model_to_world, inv, sizeof out->model_to_world);
+  return SRT_OK;
+}
+
+int SetModels(Poses* p, const srt_temporal_model* models, uint32_t n) {
+  if (!p) return SRT_ERR_INVALID;
+  if (int rc = ValidateModels(models, n)) return rc;
+  if (n) p->cur.assign(models, models + n);
+  else p->cur.clear();
+  return SRT_OK;
+}
+
+void ComposeMotion(const srt_temporal_model& pa, const srt_temporal_model& qb, float m[12]) {
+  const float* a = pa.model_to_world;
+  const float* b = qb.world_to_model;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) {
+      float e = (a[i] * b[4 * j] + a[4 + i] * b[4 * j + 1]) + a[8 + i] * b[4 * j + 2];
+      if (j == 3) e = e + a[12 + i];
+      m[4 * i + j] = e;
+    }
+}
+
+MotionRecord MotionOf(const Poses& p, uint32_t r) {
+  MotionRecord rec;
+  std::memset(&rec, 0, sizeof rec);
+  rec.m[0] = rec.m[5] = rec.m[10] = 1.0f;
+  if (r < p.prev.size() && r < p.cur.size() && std::memcmp(&p.prev[r], &p.cur[r], sizeof(srt_temporal_model)) != 0) {
+    ComposeMotion(p.prev[r], p.cur[r], rec.m);
+    rec.moving = 1;
+  }
+  return rec;
+}
+
+uint32_t FillChunk(const Poses& p, uint32_t first, MotionChunk* out) {
+  std::memset(out, 0, sizeof *out);
+  const uint32_t n = (uint32_t)p.cur.size();
+  uint32_t k = 0;
+  for (; k < kUploadChunk && first + k < n; ++k) out->r[k] = MotionOf(p, first + k);
+  return k;
+}
+
+void AdvancePoses(Poses* p) {
+  p->prev = p->cur;
+}
+
+void ResetPoses(Poses* p) {
+  p->prev.clear();
 }
 
 }  // namespace temporal

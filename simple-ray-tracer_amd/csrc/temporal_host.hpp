@@ -1,12 +1,15 @@
 // temporal_host.hpp -- host-only parts of the temporal reprojection (include/srt_temporal.h): parameter
-// validation, buffer sizing, the launch grid and the ping-pong state of the history.  No device, no HIP
-// header: tests/cpp/test_temporal_host.cpp links temporal_host.cpp alone.
+// validation, buffer sizing, the launch grid and the ping-pong state of the history, and the pose bookkeeping
+// of include/srt_temporal_motion.h.  No device, no HIP header: tests/cpp/test_temporal_host.cpp and
+// tests/cpp/test_temporal_motion_host.cpp link temporal_host.cpp alone.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/srt_temporal.h"
+#include "../../include/srt_temporal_motion.h"
 
 namespace srt {
 namespace temporal {
@@ -44,6 +47,47 @@ void Reset(History* h);
 inline int WriteIndex(const History& h) { return h.read ^ 1; }
 // After a call was enqueued: the written set becomes the one to read, `cam` the previous camera.
 void Advance(History* h, const srt_temporal_camera& cam);
+
+// ---- moving models (include/srt_temporal_motion.h) ----
+
+constexpr uint32_t kMaxModels = SRT_TEMPORAL_MAX_MODELS;
+constexpr uint32_t kUploadChunk = SRT_TEMPORAL_MODELS_PER_LAUNCH;  // records one upload launch carries by value
+
+// What the device sees per BVH record, 64 B: the rows of M_r as three 16-B words (row i = M(i,0..3)), then a
+// word whose first component is 1 for a MOVING record and 0 for a STATIC one.
+struct MotionRecord {
+  float m[12];
+  uint32_t moving;
+  uint32_t pad[3];
+};
+static_assert(sizeof(MotionRecord) == 64, "one 64-B record");
+struct MotionChunk {
+  MotionRecord r[kUploadChunk];
+};
+
+// SRT_OK; SRT_ERR_INVALID for NULL with n > 0, an entry that is not finite or a bottom row that is not exactly
+// (0, 0, 0, 1); SRT_ERR_LIMIT for n > kMaxModels.
+int ValidateModels(const srt_temporal_model* models, uint32_t n);
+int ModelFromFrame(const float frame[16], srt_temporal_model* out);
+
+// P (the poses of the previous accumulated frame; empty when there is none) and Q (the current ones).
+struct Poses {
+  std::vector<srt_temporal_model> cur;   // Q
+  std::vector<srt_temporal_model> prev;  // P
+};
+// ValidateModels, then Q = models (state unchanged on an error).
+int SetModels(Poses* p, const srt_temporal_model* models, uint32_t n);
+// M = a.model_to_world o b.world_to_model, rows of four, in the element order the header writes down.
+void ComposeMotion(const srt_temporal_model& a, const srt_temporal_model& b, float m[12]);
+// Record r of the frame about to be accumulated.  A STATIC record gets the identity, which the kernel does not
+// apply.
+MotionRecord MotionOf(const Poses& p, uint32_t r);
+// Records [first, first + kUploadChunk) of Q, zero past its end; returns how many are real.
+uint32_t FillChunk(const Poses& p, uint32_t first, MotionChunk* out);
+inline uint32_t UploadLaunches(uint32_t n) { return (n + kUploadChunk - 1) / kUploadChunk; }
+// After a call was enqueued: Q becomes P.  With the history's Reset: P is dropped, Q stays.
+void AdvancePoses(Poses* p);
+void ResetPoses(Poses* p);
 
 }  // namespace temporal
 }  // namespace srt

@@ -248,6 +248,20 @@ _TEMPORAL_SIGS = {
 }
 TEMPORAL_SYMBOLS = tuple(_TEMPORAL_SIGS)
 
+
+class TemporalModel(C.Structure):
+    """srt_temporal_model (include/srt_temporal_motion.h): both matrices column-major."""
+    _fields_ = [("world_to_model", C.c_float * 16), ("model_to_world", C.c_float * 16)]
+
+
+# include/srt_temporal_motion.h: moving models for the temporal reprojection (its own header and version)
+_TEMPORAL_MOTION_SIGS = {
+    "srt_temporal_motion_abi_version": (C.c_int, []),
+    "srt_temporal_set_models": (C.c_int, [P, C.POINTER(TemporalModel), C.c_uint32]),
+    "srt_temporal_model_from_frame": (C.c_int, [P, C.POINTER(TemporalModel)]),
+}
+TEMPORAL_MOTION_SYMBOLS = tuple(_TEMPORAL_MOTION_SIGS)
+
 _lib = None
 
 
@@ -279,7 +293,8 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items()):
+        for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
+                                  + list(_TEMPORAL_MOTION_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

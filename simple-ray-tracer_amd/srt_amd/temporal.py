@@ -5,7 +5,9 @@ new frame (a torch tensor, or the raw device pointer ``Compute.image_pointers()`
 result wherever the same surface point was visible before, and returns ``(colour, N)`` per pixel on the device;
 ``hits`` is the guide of the pixel-centre rays of ``camera`` (``Denoiser.primary_rays`` + ``Query.closest``).
 ``Denoiser.run(out, 1, hits)`` filters the result.  Nothing leaves the device and no call synchronises.  Full
-frames of a static scene only: call ``reset()`` after a scene or model-matrix change.
+frames only.  A model that moves (``UpdateModelMatrix``) is followed when ``set_models`` states the records'
+frames each frame (include/srt_temporal_motion.h); without it, call ``reset()`` after a model-matrix change, and
+after a scene change in any case.
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import TemporalCamera, TemporalParams, check, lib
+from ._lib import TemporalCamera, TemporalModel, TemporalParams, check, lib
 
 __all__ = ["Temporal"]
 
@@ -100,6 +102,27 @@ class Temporal:
     def reset(self):
         """Drop the history: the next ``accumulate`` behaves as the first."""
         check(lib().srt_temporal_reset(self.handle), "srt_temporal_reset")
+
+    def set_models(self, frames, models=None):
+        """State the pose of BVH records ``0..n-1`` for the frames accumulated from now on (it persists until set
+        again; an empty ``frames`` returns to the static behaviour).  ``frames``: ``[n, 16]`` or ``[n, 4, 4]``
+        float32, each the record's ``frame`` (world -> model) as ``UpdateModelMatrix`` takes it, glm column-major
+        (m[c][r]).  ``models``: the inverses (model -> world) in the same layout; when omitted each is computed in
+        float64 by ``srt_temporal_model_from_frame``."""
+        f = np.ascontiguousarray(np.asarray(frames, np.float32).reshape(-1, 16))
+        n = len(f)
+        arr = (TemporalModel * max(n, 1))()
+        if models is None:
+            for k in range(n):
+                check(lib().srt_temporal_model_from_frame(f[k].ctypes.data_as(C.c_void_p), C.byref(arr[k])),
+                      f"srt_temporal_model_from_frame(record {k})")
+        else:
+            m = np.ascontiguousarray(np.asarray(models, np.float32).reshape(-1, 16))
+            if len(m) != n:
+                raise ValueError("models: one model_to_world per frame")
+            both = np.ascontiguousarray(np.concatenate([f, m], axis=1))
+            C.memmove(arr, both.ctypes.data, both.nbytes)
+        check(lib().srt_temporal_set_models(self.handle, arr, n), "srt_temporal_set_models")
 
     # -- work -----------------------------------------------------------------
     def _ordered(self, torch):

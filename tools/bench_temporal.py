@@ -8,6 +8,12 @@ the same camera (every hit pixel gathers its four taps), and with the history of
 the same way in the same process: a float4 copy of one frame (the bandwidth floor) and one a-trous pass of the
 denoiser (srt_denoise_run with passes = 1), which the call is to be read against.
 Nothing is asserted: this is a measurement tool.  --out writes the JSON document (profiles/temporal.json).
+
+--motion-out (profiles/temporal_motion.json) adds the moving-model instance (include/srt_temporal_motion.h), timed
+the same way after the rows above: the call with one pose stated and unchanged (every record static: the upload
+launch plus the motion kernel), the call with the cube turned by --spin degrees since the previous frame (guides
+queried under each pose), the static instance once more beside them, and the upload launches by themselves as
+nearly as the interface allows: a 1 x 1 object's call with 0, 1 and 256 poses (its one-pixel kernel is the rest).
 """
 from __future__ import annotations
 
@@ -52,6 +58,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", help="write the results to this JSON file")
+    ap.add_argument("--motion-out", help="also time the moving-model instance and write its rows to this JSON file")
+    ap.add_argument("--spin", type=float, default=2.0, help="degrees the cube turns per frame in the moving rows")
     a = ap.parse_args()
     if a.warmup < 3 or a.reps < 10:
         ap.error("at least 3 warm-up runs and 10 measured ones")
@@ -122,6 +130,8 @@ def main():
                     "accumulate_moved_camera_ms": time_calls(torch, lambda: call(hits1, cam1), a.warmup, a.reps,
                                                              before=lambda: call(hits0, cam0)),
                 }
+                if a.motion_out:
+                    motion = motion_rows(torch, a, doc, setup, q, dn, tp, call, cam0, hits0, time_calls)
         m = doc["second_series"]["accumulate_moved_camera_ms"][0]
         doc["moved_over_copy"] = round(m / doc["second_series"]["copy_float4_frame_ms"][0], 2)
         doc["moved_over_atrous_pass"] = round(m / doc["atrous_one_pass_ms"][0], 2)
@@ -132,6 +142,75 @@ def main():
     if a.out:
         pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         pathlib.Path(a.out).write_text(json.dumps(doc, indent=1) + "\n")
+    if a.motion_out:
+        print(json.dumps(motion), flush=True)
+        pathlib.Path(a.motion_out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(a.motion_out).write_text(json.dumps(motion, indent=1) + "\n")
+
+
+def motion_rows(torch, a, doc, setup, q, dn, tp, call, cam0, hits0, time_calls):
+    """The rows of --motion-out; `call(hits, cam)` enqueues srt_temporal_accumulate on `tp`."""
+    import numpy as np
+
+    from srt_amd import _lib
+    from srt_amd.temporal import Temporal
+
+    W, H = a.width, a.height
+    v = setup.scene.verts["pos"].astype(np.float64)
+    centre = (v.min(0) + v.max(0)) / 2
+
+    def frame_of(deg):  # world -> model with the cube turned by `deg` about the vertical axis through its centre
+        c, s = np.cos(np.radians(-deg)), np.sin(np.radians(-deg))
+        m = np.eye(4)
+        m[:3, :3] = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+        m[:3, 3] = centre - m[:3, :3] @ centre
+        return m.T.reshape(16).astype(np.float32)
+
+    frames = [frame_of(0.0), frame_of(a.spin)]
+    hits = []
+    for f in frames:
+        q.update_model_matrix(0, f)
+        hits.append(q.closest(dn.primary_rays(setup.camera)))
+    q.update_model_matrix(0, frames[0])
+    out = {k: doc[k] for k in ("tool", "width", "height", "scene", "device", "code_hash", "warmup", "reps", "timing")}
+    out["spin_degrees"] = a.spin
+    out["records"] = 1
+
+    def moved_before():
+        tp.set_models([frames[0]])
+        call(hits[0], cam0)
+        tp.set_models([frames[1]])
+
+    series = []
+    for _ in range(2):  # twice: the spread between the series is the run-to-run spread the rows are read against
+        row = {}
+        tp.set_models([])
+        row["static_instance_same_camera_ms"] = time_calls(torch, lambda: call(hits0, cam0), a.warmup, a.reps)
+        tp.set_models([frames[0]])
+        row["motion_instance_all_static_ms"] = time_calls(torch, lambda: call(hits0, cam0), a.warmup, a.reps)
+        row["motion_instance_cube_moving_ms"] = time_calls(torch, lambda: call(hits[1], cam0), a.warmup, a.reps,
+                                                           before=moved_before)
+        tp.synchronize()
+        series.append(row)
+    out["series"] = series
+    moved_before()  # the share of the moved frame's hit pixels that found history
+    res = tp.accumulate(torch.ones((H, W, 4), dtype=torch.float32, device="cuda"), 1, hits[1],
+                        [list(getattr(cam0, n)) for n in ("origin", "front", "right", "up")])
+    tp.synchronize()
+    out["cube_moving_reuse_fraction_of_hits"] = round(float((res[..., 3][hits[1].hit.reshape(H, W)] >= 2).float().mean()), 4)
+    tp.set_models([])
+    with Temporal(1, 1, stream=torch.cuda.current_stream()) as tiny:
+        acc1 = torch.ones((1, 1, 4), dtype=torch.float32, device="cuda")
+        out1 = torch.empty_like(acc1)
+        hit1 = torch.zeros((1, 8), dtype=torch.int32, device="cuda")
+        for n_poses in (0, 1, 256):
+            tiny.set_models([frames[0]] * n_poses)
+            out[f"tiny_object_{n_poses}_poses_ms"] = time_calls(
+                torch, lambda: _lib.lib().srt_temporal_accumulate(tiny.handle, C.c_void_p(acc1.data_ptr()), 1,
+                                                                  C.c_void_p(hit1.data_ptr()), C.byref(cam0),
+                                                                  C.c_void_p(out1.data_ptr())), a.warmup, a.reps)
+            out[f"tiny_object_{n_poses}_poses_launches"] = tiny.get_int("launches")
+    return out
 
 
 if __name__ == "__main__":

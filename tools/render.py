@@ -1,7 +1,7 @@
 """Render a scene to an image file on the GPU: the reference's progressive loop, headless.
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
-                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K]
+                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K] [--spin DEG]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -33,7 +33,13 @@ def main():
                          "accumulation per frame as the frame loop does while the camera moves, and write the last "
                          "frame three ways: <out> (raw), <out>_denoised and <out>_temporal (accumulated over the path "
                          "by temporal reprojection, then denoised)")
+    ap.add_argument("--spin", type=float, default=0.0, metavar="DEG",
+                    help="with --orbit K: the camera stands still and the first model turns by DEG degrees per frame "
+                         "about the vertical axis through its bounds' centre; each frame's matrix goes to the renderer, "
+                         "the query and the temporal object, whose history follows the model")
     a = ap.parse_args()
+    if a.spin and not a.orbit:
+        ap.error("--spin DEG needs --orbit K")
     if a.orbit and a.scene == "spheres":
         ap.error("--orbit needs a mesh scene: the guide is a ray query")
     if a.orbit < 0:
@@ -56,7 +62,7 @@ def main():
     if a.orbit:
         try:
             t0 = time.perf_counter()
-            paths = orbit(r, setup, a.orbit, a.spp, a.out)
+            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin)
             dt = time.perf_counter() - t0
         finally:
             r.close()
@@ -106,10 +112,25 @@ def denoise(r, setup, out):
 ORBIT_STEP = (0.5, -1.0)  # per frame: MoveRight(0.5), then Rotate(-1 degree of yaw, 0): the camera circles the model
 
 
-def orbit(r, setup, frames, spp, out):
-    """`frames` frames of `spp` samples along ORBIT_STEP, each after a reset of the accumulation; every frame goes
-    through srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame
-    raw, denoised, and temporally accumulated then denoised; returns the three paths."""
+def spin_frame(scene, degrees):
+    """Record 0's `frame` (world -> model, glm column-major) with the model turned by `degrees` about the vertical
+    axis through the centre of the scene's bounds: the inverse rotation about that axis."""
+    import numpy as np
+
+    v = scene.verts["pos"].astype(np.float64)
+    centre = (v.min(0) + v.max(0)) / 2
+    c, s = np.cos(np.radians(-degrees)), np.sin(np.radians(-degrees))
+    m = np.eye(4)
+    m[:3, :3] = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
+    m[:3, 3] = centre - m[:3, :3] @ centre
+    return m.T.reshape(16).astype(np.float32)
+
+
+def orbit(r, setup, frames, spp, out, spin=0.0):
+    """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
+    (degrees per frame) under a still camera while the first model turns.  Every frame goes through
+    srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame raw,
+    denoised, and temporally accumulated then denoised; returns the three paths."""
     import srt_amd as S
     from srt_amd.denoise import Denoiser
     from srt_amd.query import Query
@@ -122,7 +143,12 @@ def orbit(r, setup, frames, spp, out):
     with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, Query(setup.scene) as q:
         q.set_bvh_count(setup.bvh_count)
         for k in range(frames):
-            if k:
+            if spin:  # the three per-frame calls of a moving model
+                frame = spin_frame(setup.scene, spin * (k + 1))
+                S.UpdateModelMatrix(c, 0, frame)
+                q.update_model_matrix(0, frame)
+                tp.set_models([frame])
+            elif k:
                 cam.MoveRight(ORBIT_STEP[0])
                 cam.Rotate(ORBIT_STEP[1], 0.0)
                 c.SetVec3("cameraOrigin", cam.getOrigin())
