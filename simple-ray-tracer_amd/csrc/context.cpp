@@ -8,6 +8,7 @@
 #include "context.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -177,6 +178,8 @@ int srt_create(int device, void* stream, srt_context** out) {
   if (const char* e = std::getenv("SRT_TAIL_CLAIMS"))
     c->tail_claims = c->tail_claims_sph = c->tail_claims_gw5 = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("SRT_TILE_ORDER")) c->tile_schedule = e[0] != '0';
+  if (const char* e = std::getenv("SRT_TILE_CULL")) c->tile_cull = e[0] != '0';
+  if (const char* e = std::getenv("SRT_TILE_CULL_MIN_SAMPLES")) c->cull_min_samples = std::max(0LL, std::atoll(e));
   if (const char* e = std::getenv("SRT_TRAV_FRAC16")) c->trav_frac16 = std::max(0, std::min(16, std::atoi(e)));
   if (const char* e = std::getenv("SRT_TRAV_FRAC16_GLOBAL"))
     c->trav_frac16_global = std::max(0, std::min(16, std::atoi(e))), c->trav_frac16_global_env = true;
@@ -229,6 +232,14 @@ int srt_destroy(srt_context* c) {
   FreeDev(c->d_tex); FreeDev(c->d_tex_info); FreeDev(c->d_tri_uv);
   FreeDev(c->d_noise_xy); FreeDev(c->d_noise_u); FreeDev(c->d_stats); FreeDev(c->d_nan); FreeDev(c->d_lbuf); FreeDev(c->d_gstack);
   FreeDev(c->d_batch_ctr); FreeDev(c->d_tile_cost); FreeDev(c->d_tile_order); FreeDev(c->d_row_map); FreeDev(c->d_span);
+  for (auto& e : c->cull_ring) {
+    FreeDev(e.d_live); FreeDev(e.d_sky);
+    if (e.h_live) (void)hipHostFree(e.h_live);
+    if (e.h_sky) (void)hipHostFree(e.h_sky);
+    if (e.ready) (void)hipEventDestroy(e.ready);
+    if (e.used) (void)hipEventDestroy(e.used);
+  }
+  if (c->cull_stream) (void)hipStreamDestroy(c->cull_stream);
   FreeDev(c->d_wf_rec); FreeDev(c->d_wf_res); FreeDev(c->d_wf_state); FreeDev(c->d_wf_rayq); FreeDev(c->d_wf_hitq);
   FreeDev(c->d_wf_ctl); FreeDev(c->d_wf_items);
   FreeDev(c->d_nodes_t); FreeDev(c->d_troot); FreeDev(c->d_tl_ray); FreeDev(c->d_tl_stk); FreeDev(c->d_tl_slist);
@@ -333,6 +344,10 @@ int srt_get_int(srt_context* c, const char* name, int* v) {
   else if (n == "launch.blocks_per_cu") *v = c->launch_per_cu;      // resident blocks per CU of the last sample launch
   else if (n == "launch.block") *v = c->launch_block;               // its lanes per block
   else if (n == "launch.mats_lds") *v = c->launch_mats_lds;          // 1: it read the material records from LDS
+  else if (n == "launch.live_tiles") *v = c->launch_live_tiles;      // tiles its launches traced (tile_cull.hpp)
+  else if (n == "cull.uploads") *v = (int)std::min<unsigned long long>(c->cull_uploads, 0x7FFFFFFF);  // maps sent to the device
+  else if (n == "launch.culled_samples")                             // samples the last render did not trace
+    *v = (int)std::min<long long>(c->launch_culled, 0x7FFFFFFF);
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -434,10 +449,21 @@ int srt_set_noise(srt_context* c, const float* noise_rgb, const float* noise_u_r
   if (int rq = Quiesce(c)) return rq;
   std::vector<float2> xy(texels);
   std::vector<float> u(texels);
+  // (and the exact extremes of the jitter, which bound every sample's place in its pixel: tile_cull.hpp)
+  float mn[2] = {noise_rgb[0], noise_rgb[1]}, mx[2] = {noise_rgb[0], noise_rgb[1]};
+  bool finite = true;
   for (size_t i = 0; i < texels; ++i) {
     xy[i] = make_float2(noise_rgb[3 * i], noise_rgb[3 * i + 1]);
     u[i] = noise_u_rgb[3 * i];
+    for (int k = 0; k < 2; ++k) {
+      const float v = noise_rgb[3 * i + k];
+      finite = finite && std::isfinite(v);
+      mn[k] = std::min(mn[k], v);
+      mx[k] = std::max(mx[k], v);
+    }
   }
+  c->noise_finite = false;  // (until the upload below has succeeded)
+  ++c->cull_gen;
   if (texels != c->noise_texels) {
     FreeDev(c->d_noise_xy); FreeDev(c->d_noise_u);
     c->d_noise_xy = nullptr; c->d_noise_u = nullptr; c->noise_texels = 0;
@@ -448,6 +474,8 @@ int srt_set_noise(srt_context* c, const float* noise_rgb, const float* noise_u_r
   HIP_OK(hipMemcpyAsync(c->d_noise_u, u.data(), texels * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
   c->noise_texels = texels;
+  for (int k = 0; k < 2; ++k) c->nz_min[k] = mn[k], c->nz_max[k] = mx[k];
+  c->noise_finite = finite;
   return SRT_OK;
 }
 

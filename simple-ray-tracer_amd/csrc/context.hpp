@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "srt_internal.hpp"
+#include "tile_cull.hpp"
 
 #define HIP_OK(expr)                                                                          \
   do {                                                                                        \
@@ -89,6 +90,42 @@ struct srt_context {
   uint32_t* d_tile_order = nullptr;
   int tile_cap = 0, tile_costs_for = -1;
   bool tile_schedule = true;  // SRT_TILE_ORDER=0: natural tile order
+  // Tile culling (tile_cull.hpp): the timed launches of a mesh scene trace only the tiles that are not
+  // provably sky.  The classification is recomputed when what it reads changes (cull_key: camera, extent,
+  // frame, tiling, BVH records, noise, launch kind), never per chunk.  Its device copies go through a small
+  // ring of buffers: a new map is written to pinned staging and copied on cull_stream into the next entry,
+  // the launch's streams wait for that copy, and an entry is reused only after the last launch that read it
+  // (its `used` event), which the host waits for.  No launch is drained, but that wait and the copy cost a
+  // host that runs ahead of the GPU about 0.25 ms per new map, so a launch that culls fewer than
+  // cull_min_samples samples keeps the map already on the device or runs all-live (pathtrace.hip EnsureTileCull).
+  bool tile_cull = true;              // SRT_TILE_CULL=0: every tile stays live
+  long long cull_min_samples = 1ll << 24;  // SRT_TILE_CULL_MIN_SAMPLES: culled samples a launch needs for a new map
+  bool roots_ok = false;              // h_roots holds every uploaded record's root box
+  std::vector<srt::RootBox> h_roots;  // root box of each uploaded record's tree
+  std::vector<int> h_row_map;         // host copy of d_row_map
+  float nz_min[2] = {0, 0}, nz_max[2] = {0, 0};  // extremes of noise_xy (srt_set_noise)
+  bool noise_finite = false;
+  unsigned long long cull_gen = 0;    // bumped by whatever the key cannot hold: BVH records, noise
+  std::vector<unsigned char> cull_key;
+  int cull_live = 0;                  // of the classification for cull_key: its live tiles, and the in-extent
+  long long cull_pixels = 0;          // pixels of its sky tiles
+  struct CullBuf {
+    uint32_t* d_live = nullptr;       // the live tiles' indices, ascending
+    uint8_t* d_sky = nullptr;         // per tile: 1 = sky
+    uint32_t* h_live = nullptr;       // pinned staging of both
+    uint8_t* h_sky = nullptr;
+    int cap = 0;
+    hipEvent_t ready = nullptr, used = nullptr;  // the copy has landed / the last launch reading it has ended
+    bool ready_rec = false, used_rec = false;
+  };
+  static constexpr int kCullRing = 4;
+  CullBuf cull_ring[kCullRing];
+  int cull_cur = -1;                  // the entry holding h_tile_sky (-1: none yet)
+  std::vector<uint8_t> h_tile_sky;    // the map in cull_ring[cull_cur]
+  hipStream_t cull_stream = nullptr;
+  unsigned long long cull_uploads = 0;  // maps sent to the device since create (cull.uploads)
+  int launch_live_tiles = 0;          // of the last render's launches (launch.live_tiles)
+  long long launch_culled = 0;        // samples the last render did not trace (launch.culled_samples)
   int* d_row_map = nullptr;           // nranks > 1: global row of each local row (KParams::row_map)
   long long row_map_key = -1;         // the (rank, nranks, band_rows, rows) it was built for
   unsigned long long* d_batch_ctr = nullptr;  // one batch counter per chunk launch

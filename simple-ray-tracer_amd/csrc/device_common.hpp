@@ -73,6 +73,8 @@ struct KParams {
   int mats_lds, mats_base_f4, mat_records;  // mat_records records of 2 float4
   const uint32_t* tile_order;  // the launch's tiles in schedule order (nullptr: natural order)
   uint32_t* tile_cost;         // per tile: first-frame bounces recorded for the next launch's order (or nullptr)
+  int live_tiles;              // entries of tile_order: the tiles the launch traces (every tile, or the ones not `sky`)
+  const uint8_t* tile_sky;     // per tile: 1 = never traced, accumulate_kernel supplies the sky constant (nullptr: none)
   unsigned long long* wave_trace;  // diagnostic build (SRT_WAVE_TRACE): 4 stamps per wave
   unsigned long long* span;        // {first wave's start, last wave's end} (s_memrealtime, 100 MHz), or nullptr
   const int* row_map;      // nranks > 1: the global row of each local row (row bands, pathtrace.hip FillParams)

@@ -75,6 +75,10 @@ __host__ __device__ constexpr int global_ring(int gw) { return (gw > 4 || SRT_CO
 // Returns what the path traces next: kShadeShadow (CheckLightOccluded's ray, ro/rd/tmax set,
 // the bounce direction in nd), kShadeBounce (the next CheckHit ray) or kShadeDone.
 enum { kShadeDone = 0, kShadeShadow = 1, kShadeBounce = 2 };
+// skyColor (raytrace_compute.glsl:219,292): what a path that leaves the scene adds, times its throughput.
+// finish_sample adds it; accumulate_kernel supplies 0 + (1,1,1) * sky for the samples of a `sky` tile
+// (tile_cull.hpp), which sample_kernel never traces.
+__device__ __forceinline__ f3 sky_color() { return mk(0.05f, 0.05f, 0.05f); }
 // SPH: the sphere scene's instance (sphere_kernel); every other caller is a mesh scene (showModel set).
 template <bool COUNT, bool LDSM, bool TEX, bool SPH = false>
 __device__ __forceinline__ int shade_hit(const KParams& kp, const Lane& ln, Counters& c, uint32_t ht, int hit_sphere,
@@ -307,7 +311,7 @@ __device__ __forceinline__ void sample_body(const KParams& kp) {
 
   const f3 center = mk(kp.cx, kp.cy, kp.cz);
   const int tiles_x = (kp.W + 7) >> 3;
-  const int n_tiles = tiles_x * ((kp.local_rows + 7) >> 3);
+  const int n_tiles = kp.live_tiles;  // entries of kp.tile_order (pathtrace.hip Launch: the tiles not `sky`)
   const int n_batches = n_tiles * kp.nframes;  // < 2^31: the host bounds the frames per launch
   // batches are claimed from a launch-wide counter of batches, so waves that
   // drew cheap tiles take more of them (no static-share tail).  A claim takes
@@ -378,7 +382,7 @@ __device__ __forceinline__ void sample_body(const KParams& kp) {
       const int ly = li / kp.W, px = li - ly * kp.W;
       atomicAdd(&kp.tile_cost[(ly >> 3) * tiles_x + (px >> 3)], (uint32_t)(bounces + 1));
     }
-    color = color + T * mk(0.05f, 0.05f, 0.05f);  // skyColor, raytrace_compute.glsl:219,292
+    color = color + T * sky_color();  // raytrace_compute.glsl:219,292
     if constexpr (SRT_NT_SAMPLES || (SPH && SRT_NT_SPH)) {
       // streaming store: the sample buffer passes through L2 once, and would evict the noise tables
       typedef float v4f __attribute__((ext_vector_type(4)));
@@ -424,7 +428,7 @@ __device__ __forceinline__ void sample_body(const KParams& kp) {
 #if SRT_TILE_SCHED
       const int tile = (int)((const __attribute__((address_space(4))) uint32_t*)(kp.tile_order))[trank];
 #else
-      const int tile = trank;
+      const int tile = trank;  // (such a build cannot deal a list of live tiles: the host then culls none, EnsureTileCull)
 #endif
       const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
       const int samp = (kp.frame_first + frame_i) % kp.WH;
@@ -658,11 +662,13 @@ __device__ __forceinline__ int cost_bucket(uint32_t c) {
   const int b = (int)(__log2f((float)c + 1.0f) * 4.0f);
   return b < 63 ? b : 63;
 }
-__global__ __launch_bounds__(1024) void order_tiles_kernel(uint32_t* cost, uint32_t* order, int n) {
+// `live`: the n tiles to order (a timed launch's tiles that are not `sky`; their costs alone are read and
+// reset), or nullptr for tiles 0 .. n - 1.
+__global__ __launch_bounds__(1024) void order_tiles_kernel(uint32_t* cost, uint32_t* order, const uint32_t* live, int n) {
   __shared__ uint32_t hist[64];
   if (threadIdx.x < 64) hist[threadIdx.x] = 0;
   __syncthreads();
-  for (int i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&hist[cost_bucket(cost[i])], 1u);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&hist[cost_bucket(cost[live ? live[i] : (uint32_t)i])], 1u);
   __syncthreads();
   if (threadIdx.x == 0) {  // exclusive offsets, most expensive bucket first
     uint32_t s = 0;
@@ -674,8 +680,9 @@ __global__ __launch_bounds__(1024) void order_tiles_kernel(uint32_t* cost, uint3
   }
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    order[atomicAdd(&hist[cost_bucket(cost[i])], 1u)] = (uint32_t)i;
-    cost[i] = 0u;
+    const uint32_t t = live ? live[i] : (uint32_t)i;
+    order[atomicAdd(&hist[cost_bucket(cost[t])], 1u)] = t;
+    cost[t] = 0u;
   }
 }
 
@@ -687,9 +694,9 @@ __global__ void span_init_kernel(unsigned long long* span) {
   }
 }
 
-__global__ __launch_bounds__(256) void iota_kernel(uint32_t* order, int n) {
+__global__ __launch_bounds__(256) void iota_kernel(uint32_t* order, const uint32_t* live, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) order[i] = (uint32_t)i;
+  if (i < n) order[i] = live ? live[i] : (uint32_t)i;
 }
 
 // Ordered sum of the sample buffer into the accumulation image (raytrace_compute.glsl:
@@ -705,9 +712,13 @@ __global__ __launch_bounds__(256) void accumulate_kernel(KParams kp, int out_fra
   const float4 a0 = kp.accum[li];
   f3 acc = mk(a0.x, a0.y, a0.z);
   const float4* L = kp.lbuf + li;
+  // a `sky` tile's samples were never traced (their sample-buffer rows are untouched): each is the value
+  // finish_sample stores for a camera ray that leaves the scene, added in the same loop, in the same order
+  const bool sky = kp.tile_sky && kp.tile_sky[(ly >> 3) * ((kp.W + 7) >> 3) + (x >> 3)];
+  const f3 skyv = mk(0.0f, 0.0f, 0.0f) + mk(1.0f, 1.0f, 1.0f) * sky_color();
   uint32_t nan = 0;
   for (int k = 0; k < kp.nframes; ++k) {
-    const float4 s = L[(size_t)k * (size_t)kp.local_pixels];
+    const float4 s = sky ? make_float4(skyv.x, skyv.y, skyv.z, 0.0f) : L[(size_t)k * (size_t)kp.local_pixels];
     acc = acc + mk(s.x, s.y, s.z);
     nan += ((s.x != s.x) | (s.y != s.y) | (s.z != s.z)) ? 1u : 0u;
   }

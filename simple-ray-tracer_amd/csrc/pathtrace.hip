@@ -39,6 +39,7 @@
 #include "launch_plan.hpp"
 #include "scene_image.hpp"
 #include "scene_layout.hpp"
+#include "tile_cull.hpp"
 
 // ===========================================================================
 // host side: the launches behind the C ABI
@@ -177,6 +178,7 @@ int FillParams(srt_context* c, srt::KParams* kp, bool need_images) {
       HIP_OK(hipMemcpyAsync(c->d_row_map, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
       HIP_OK(hipStreamSynchronize(c->stream));
       c->row_map_key = key;
+      c->h_row_map = std::move(rows);
     }
     kp->row_map = c->d_row_map;
   }
@@ -267,7 +269,7 @@ int LaunchSamples(srt_context* c, srt::KParams kp, size_t lds) {
   {  // single-batch claims for the last tail_claims * kClaim batches per wave (sample_kernel; measured
      // in round 1: 2 -> 16 halves the launch's tail)
     const long long waves = (long long)blocks * (BLOCK / 64);
-    const long long n_batches = (long long)((kp.W + 7) >> 3) * ((kp.local_rows + 7) >> 3) * kp.nframes;
+    const long long n_batches = (long long)kp.live_tiles * kp.nframes;
     const int tail_claims = (FUSE && GW == 5 && !TEX) ? c->tail_claims_gw5 : c->tail_claims;
     kp.tail_start = (int)std::max<long long>(0, n_batches - (long long)tail_claims * srt::kClaim * waves);
   }
@@ -302,7 +304,7 @@ int LaunchSpheres(srt_context* c, srt::KParams kp, size_t lds) {
   c->launch_block = 256;
   {
     const long long waves = (long long)blocks * 4;
-    const long long n_batches = (long long)((kp.W + 7) >> 3) * ((kp.local_rows + 7) >> 3) * kp.nframes;
+    const long long n_batches = (long long)kp.live_tiles * kp.nframes;
     kp.tail_start = (int)std::max<long long>(0, n_batches - (long long)c->tail_claims_sph * srt::kClaimSph * waves);
   }
   if (int rs = TakeSpan(c, kp)) return rs;
@@ -556,6 +558,114 @@ int LaunchWavefront(srt_context* c, srt::KParams kp, bool tex) {
   return SRT_OK;
 }
 
+// The sky / live classification of the launch's tiles (tile_cull.hpp): recomputed on the host when something it
+// reads has changed (tens of microseconds), and sent to the device -- the live tiles' list for the tile order,
+// the per-tile map for accumulate_kernel -- when its result differs from the map there and the launch repays
+// it.  Sending a map is not free: the copy runs on a stream of its own, the launch's streams wait for it, and
+// the host waits for the last reader of the ring entry it rewrites -- measured at 0.25 ms per launch on a host
+// that runs ahead of the GPU (profiles/r07_tile_cull.txt), against 19 ps saved per culled sample.  So a launch
+// that would need a map other than the one on the device, and culls fewer than cull_min_samples samples
+// (SRT_TILE_CULL_MIN_SAMPLES, default 2^24: about 1.3 times the break-even), runs with every tile live
+// instead: a camera that moves every frame at a few spp pays the classification alone.  A context's first map
+// is always sent (nothing reads the ring yet).  *use: the entry whose tiles the launch deals (nullptr: every
+// tile is live).
+int EnsureTileCull(srt_context* c, const srt::KParams& kp, int n_tiles, bool count, bool pool_or_wf,
+                   srt_context::CullBuf** use) {
+  *use = nullptr;
+  std::vector<unsigned char> key;
+  const auto put = [&key](const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    key.insert(key.end(), b, b + n);
+  };
+  const float cam[12] = {kp.cx, kp.cy, kp.cz, kp.p00x, kp.p00y, kp.p00z, kp.dux, kp.duy, kp.duz, kp.dvx, kp.dvy, kp.dvz};
+  const long long ints[14] = {kp.W, kp.H, kp.local_rows, kp.ext_w, kp.ext_h, kp.rank, kp.nranks, kp.band_rows,
+                              (long long)kp.bvh_count, (long long)c->cull_gen, kp.show_model, count, pool_or_wf,
+                              kp.nframes};
+  put(cam, sizeof cam);
+  put(ints, sizeof ints);
+  // a launch too small to repay a new map even if every sample were culled is not classified either (the
+  // cache is left alone, so a launch whose key it holds still uses it): every tile live
+  if (key != c->cull_key && c->cull_cur >= 0 &&
+      (long long)kp.W * kp.local_rows * (long long)kp.nframes < c->cull_min_samples)
+    return SRT_OK;
+  if (key != c->cull_key) {
+    srt::TileCullIn in;
+    for (int i = 0; i < 3; ++i) in.center[i] = cam[i], in.p00[i] = cam[3 + i], in.du[i] = cam[6 + i], in.dv[i] = cam[9 + i];
+    in.W = kp.W;
+    in.H = kp.H;
+    in.local_rows = kp.local_rows;
+    in.ext_w = kp.ext_w;
+    in.ext_h = kp.ext_h;
+    in.row_map = kp.nranks > 1 ? c->h_row_map.data() : nullptr;
+    in.bvhs = c->h_bvhs.data();
+    in.roots = c->h_roots.data();
+    in.n_records = c->h_bvhs.size();
+    in.bvh_count = kp.bvh_count;
+    for (int k = 0; k < 2; ++k) in.nz_min[k] = c->nz_min[k], in.nz_max[k] = c->nz_max[k];
+    in.noise_finite = c->noise_finite;
+    in.show_model = kp.show_model != 0;
+    in.counting = count;
+    in.pool_or_wavefront = pool_or_wf;
+    // (a build that ignores kp.tile_order cannot deal a list of tiles; no root boxes: nothing to test against)
+    in.enabled = c->tile_cull && SRT_TILE_SCHED != 0 && c->roots_ok && c->h_roots.size() == c->h_bvhs.size() &&
+                 (kp.nranks == 1 || (int)c->h_row_map.size() >= kp.local_rows);
+    srt::TileCullOut out;
+    srt::ClassifyTiles(in, &out);
+    if ((int)out.sky.size() != n_tiles) {
+      srt::SetError("tile classification and launch plan disagree on the tile count");
+      return SRT_ERR_STATE;
+    }
+    const bool differs = out.live < n_tiles && (c->cull_cur < 0 || out.sky != c->h_tile_sky);
+    if (differs && c->cull_cur >= 0 && out.culled_pixels * (long long)kp.nframes < c->cull_min_samples) {
+      out.live = n_tiles;  // the launch cannot repay a new map: every tile live, the device's map stays
+      out.culled_pixels = 0;
+    } else if (differs) {
+      const int next = (c->cull_cur + 1) % srt_context::kCullRing;
+      srt_context::CullBuf& e = c->cull_ring[next];
+      if (!c->cull_stream) HIP_OK(hipStreamCreateWithFlags(&c->cull_stream, hipStreamNonBlocking));
+      if (!e.ready) {
+        HIP_OK(hipEventCreateWithFlags(&e.ready, hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(&e.used, hipEventDisableTiming));
+      }
+      // the entry's last copy and the last launch that read it (four maps ago: long over)
+      if (e.ready_rec) HIP_OK(hipEventSynchronize(e.ready));
+      if (e.used_rec) HIP_OK(hipEventSynchronize(e.used));
+      if (n_tiles > e.cap) {
+        FreeDev(e.d_live);
+        FreeDev(e.d_sky);
+        if (e.h_live) (void)hipHostFree(e.h_live);
+        if (e.h_sky) (void)hipHostFree(e.h_sky);
+        e.d_live = e.h_live = nullptr;
+        e.d_sky = e.h_sky = nullptr;
+        e.cap = 0;
+        HIP_OK(hipMalloc(&e.d_live, sizeof(uint32_t) * (size_t)n_tiles));
+        HIP_OK(hipMalloc(&e.d_sky, (size_t)n_tiles));
+        HIP_OK(hipHostMalloc(&e.h_live, sizeof(uint32_t) * (size_t)n_tiles, hipHostMallocDefault));
+        HIP_OK(hipHostMalloc(&e.h_sky, (size_t)n_tiles, hipHostMallocDefault));
+        e.cap = n_tiles;
+      }
+      int nl = 0;
+      for (int t = 0; t < n_tiles; ++t) {
+        e.h_sky[t] = out.sky[(size_t)t];
+        if (!out.sky[(size_t)t]) e.h_live[nl++] = (uint32_t)t;
+      }
+      if (nl > 0) HIP_OK(hipMemcpyAsync(e.d_live, e.h_live, sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, c->cull_stream));
+      HIP_OK(hipMemcpyAsync(e.d_sky, e.h_sky, (size_t)n_tiles, hipMemcpyHostToDevice, c->cull_stream));
+      HIP_OK(hipEventRecord(e.ready, c->cull_stream));
+      e.ready_rec = true;
+      e.used_rec = false;
+      c->cull_cur = next;
+      c->h_tile_sky = std::move(out.sky);
+      ++c->cull_uploads;
+    }
+    c->cull_live = out.live;
+    c->cull_pixels = out.culled_pixels;
+    c->cull_key = std::move(key);
+  }
+  if (c->cull_live < n_tiles) *use = &c->cull_ring[c->cull_cur];
+  return SRT_OK;
+}
+
 // Runs frames kp.frame_first .. + kp.nframes - 1 (or the reset frame) through
 // sample_kernel + accumulate_kernel, in chunks that fit the sample buffer.
 int Launch(srt_context* c, srt::KParams& kp, bool count) {
@@ -615,6 +725,15 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
   const size_t n_tiles = chunks.n_tiles, need = chunks.need;
   const int chunk = chunks.chunk, nchunks = chunks.nchunks;
   const bool piped = !count && !pool && !wf && c->pipe > 1;
+  // timed sample_kernel launches of a mesh scene deal only the tiles that are not provably sky; counting
+  // launches keep every tile (their counts stay the reference's), as do the sphere scene, pool and wavefront mode
+  srt_context::CullBuf* cullbuf = nullptr;
+  if (int rt = EnsureTileCull(c, kp, (int)n_tiles, count, pool || wf, &cullbuf)) return rt;
+  const bool cull = cullbuf != nullptr;
+  const int n_live = cull ? c->cull_live : (int)n_tiles;
+  const uint32_t* live_list = cull ? cullbuf->d_live : nullptr;
+  c->launch_live_tiles = n_live;
+  c->launch_culled = cull ? c->cull_pixels * (long long)kp.nframes : 0;
   // (a counting launch, the untimed first launch of a measurement, sets the slots up for the timed ones)
   if ((piped || (count && c->pipe > 1)) && c->slots.empty()) {
     c->slots.resize((size_t)c->pipe);
@@ -716,10 +835,20 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
           c->tile_cap = nt;
           c->tile_costs_for = -1;
         }
+        // the live tiles' list and the sky map may still be on their way (EnsureTileCull)
+        if (cull && hipStreamWaitEvent(ls, cullbuf->ready, 0) != hipSuccess) { rc = HipFail("sample launch"); break; }
+        if (cull && ls != c->stream && hipStreamWaitEvent(c->stream, cullbuf->ready, 0) != hipSuccess) { rc = HipFail("sample launch"); break; }
+        // (the costs are kept per tile, so they stay good when the live set changes; a sky tile's is neither
+        // read nor written, so a tile that turns live again is placed by the cost its last live launch left:
+        // that only moves it in the schedule)
         if (c->tile_schedule && c->tile_costs_for == nt) {
-          hipLaunchKernelGGL(srt::order_tiles_kernel, dim3(1), dim3(1024), 0, ls, c->d_tile_cost, c->d_tile_order, nt);
+          if (n_live > 0)
+            hipLaunchKernelGGL(srt::order_tiles_kernel, dim3(1), dim3(1024), 0, ls, c->d_tile_cost, c->d_tile_order,
+                               live_list, n_live);
         } else {
-          hipLaunchKernelGGL(srt::iota_kernel, dim3((nt + 255) / 256), dim3(256), 0, ls, c->d_tile_order, nt);
+          if (n_live > 0)
+            hipLaunchKernelGGL(srt::iota_kernel, dim3((n_live + 255) / 256), dim3(256), 0, ls, c->d_tile_order, live_list,
+                               n_live);
           if (c->tile_schedule && hipMemsetAsync(c->d_tile_cost, 0, sizeof(uint32_t) * (size_t)nt, ls) != hipSuccess) {
             rc = HipFail("sample launch");
             break;
@@ -727,6 +856,8 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
         }
         if (hipGetLastError() != hipSuccess) { rc = HipFail("sample launch"); break; }
         kc.tile_order = c->d_tile_order;
+        kc.live_tiles = n_live;
+        kc.tile_sky = cull ? cullbuf->d_sky : nullptr;
         kc.tile_cost = c->tile_schedule ? c->d_tile_cost : nullptr;
         c->tile_costs_for = c->tile_schedule ? nt : -1;
       }
@@ -756,6 +887,10 @@ int Launch(srt_context* c, srt::KParams& kp, bool count) {
       }
       hipLaunchKernelGGL(srt::accumulate_kernel, pgrid, dim3(256), 0, c->stream, kc, out_frames);
       if (hipGetLastError() != hipSuccess) { rc = HipFail("sample launch"); break; }
+      if (cull) {  // the map's entry may be rewritten once this launch's kernels have read it
+        if (hipEventRecord(cullbuf->used, c->stream) != hipSuccess) { rc = HipFail("sample launch"); break; }
+        cullbuf->used_rec = true;
+      }
       if (sl) {
         if (hipEventRecord(sl->accumulated, c->stream) != hipSuccess) { rc = HipFail("sample launch"); break; }
         sl->pending = true;
@@ -961,6 +1096,18 @@ int srt_upload_scene(srt_context* c, const srt_bvh_record* bvhs, uint32_t n_bvhs
   if ((rc = UploadArray(c, &c->d_tris, img.tris))) return rc;
   HIP_OK(hipStreamSynchronize(c->stream));
   c->h_bvhs = std::move(img.bvhs);
+  c->h_roots.assign(c->h_bvhs.size(), srt::RootBox{});  // each record's root box, as the kernels read it (tile_cull.hpp)
+  c->roots_ok = true;
+  for (size_t i = 0; i < c->h_bvhs.size(); ++i) {
+    const size_t at = 2 * (size_t)c->h_bvhs[i].first_index + 2;
+    if (at + 2 > img.nodes.size()) {  // no box to read: culling stays off for this scene (EnsureTileCull)
+      c->roots_ok = false;
+      break;
+    }
+    const float4 lo = img.nodes[at], hi = img.nodes[at + 1];
+    c->h_roots[i] = srt::RootBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+  }
+  ++c->cull_gen;
   c->bvh_tris = std::move(img.bvh_tris);
   c->sample_textures = img.sampled;
   c->bvhs_dirty = true;
@@ -1043,6 +1190,7 @@ int srt_update_model_matrix(srt_context* c, uint32_t index, const float frame[16
   }
   std::memcpy(c->h_bvhs[index].frame, frame, sizeof(float) * 16);
   c->bvhs_dirty = true;
+  ++c->cull_gen;
   return SRT_OK;  // pushed to the device at the next launch (EnsureBvhs)
 }
 
