@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../srt_denoise.h"
+#include "../srt_variance.h"
 
 namespace srt {
 
@@ -44,6 +45,22 @@ class Denoiser {
   void run(const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev, void* out_rgba32f_dev,
            void* out_rgba8_dev) {
     Check(srt_denoise_run(d_, accum_rgba32f_dev, frames, guide_dev, out_rgba32f_dev, out_rgba8_dev), "srt_denoise_run");
+  }
+  // The variance-guided filter (srt_variance.h): allocate the variance arrays once; 1 + passes launches a run.
+  void EnableVariance() { Check(srt_denoise_enable_variance(d_), "srt_denoise_enable_variance"); }
+  srt_denoise_var_params variance_params() const {
+    srt_denoise_var_params p{};
+    Check(srt_denoise_get_var_params(d_, &p), "srt_denoise_get_var_params");
+    return p;
+  }
+  void SetVarianceParams(const srt_denoise_var_params& p) {
+    Check(srt_denoise_set_var_params(d_, &p), "srt_denoise_set_var_params");
+  }
+  void RunVariance(const void* colour_rgba32f_dev, int frames, const srt_hit* guide_dev, const void* moments_dev,
+                   void* out_rgba32f_dev, void* out_rgba8_dev, void* out_var_f32_dev) {
+    Check(srt_denoise_run_variance(d_, colour_rgba32f_dev, frames, guide_dev, moments_dev, out_rgba32f_dev, out_rgba8_dev,
+                                   out_var_f32_dev),
+          "srt_denoise_run_variance");
   }
   int get_int(const char* name) const {
     int v = 0;

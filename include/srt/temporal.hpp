@@ -8,6 +8,7 @@
 
 #include "../srt_temporal.h"
 #include "../srt_temporal_motion.h"
+#include "../srt_variance.h"
 
 namespace srt {
 
@@ -54,6 +55,13 @@ class Temporal {
                   void* out_rgba32f_dev) {
     Check(srt_temporal_accumulate(t_, accum_rgba32f_dev, frames, guide_dev, &cam, out_rgba32f_dev),
           "srt_temporal_accumulate");
+  }
+  // Luminance moments (srt_variance.h): allocate their history once, then accumulate with out_moments = (m1, m2, v, N).
+  void EnableMoments() { Check(srt_temporal_enable_moments(t_), "srt_temporal_enable_moments"); }
+  void AccumulateMoments(const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev, const srt_temporal_camera& cam,
+                         void* out_rgba32f_dev, void* out_moments_dev) {
+    Check(srt_temporal_accumulate_moments(t_, accum_rgba32f_dev, frames, guide_dev, &cam, out_rgba32f_dev, out_moments_dev),
+          "srt_temporal_accumulate_moments");
   }
   int get_int(const char* name) const {
     int v = 0;

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/srt_denoise.h"
+#include "../../include/srt_variance.h"
 #include "denoise.hpp"
 #include "denoise_host.hpp"
 
@@ -29,6 +30,8 @@ struct srt_denoiser {
   float4* d_color[2] = {nullptr, nullptr};  // ping-pong colour | id
   float4* d_guide = nullptr;                // normal | t
   srt_denoise_params params;
+  float* d_var[2] = {nullptr, nullptr};     // ping-pong variance (include/srt_variance.h); srt_denoise_enable_variance
+  srt_denoise_var_params var_params;
   int tile_max_step = 0;
   int last_launches = 0;
 };
@@ -43,6 +46,8 @@ void FreeAll(srt_denoiser* dn) {
   for (float4* p : dn->d_color)
     if (p) (void)hipFree(p);
   if (dn->d_guide) (void)hipFree(dn->d_guide);
+  for (float* p : dn->d_var)
+    if (p) (void)hipFree(p);
   if (dn->own_stream && dn->stream) (void)hipStreamDestroy(dn->stream);
 }
 
@@ -87,6 +92,7 @@ int srt_denoise_create(int device, void* stream, int width, int height, srt_deno
   dn->height = height;
   dn->sizes = sizes;
   dn->params = srt::denoise::DefaultParams();
+  dn->var_params = srt::denoise::DefaultVarParams();
   dn->tile_max_step = srt::denoise::TileMaxStep(std::getenv("SRT_DENOISE_TILE"));
   if (int rc = Allocate(dn)) {
     FreeAll(dn);
@@ -121,6 +127,10 @@ int srt_denoise_get_int(srt_denoiser* dn, const char* name, int* v) {
   else if (n == "tile.width") *v = srt::denoise::kTileW;
   else if (n == "tile.height") *v = srt::denoise::kTileH;
   else if (n == "launches") *v = dn->last_launches;
+  else if (n == "variance.bytes") {
+    const size_t b = dn->d_var[0] ? 2 * srt::denoise::VarianceBytes(dn->sizes) : 0;
+    *v = (int)(b < 0x7FFFFFFFu ? b : 0x7FFFFFFFu);
+  }
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -217,6 +227,98 @@ int srt_denoise_run(srt_denoiser* dn, const void* accum_rgba32f_dev, int frames,
       else
         hipLaunchKernelGGL(srt::denoise::denoise_direct_kernel<false>, grid, dim3(kBlock), 0, dn->stream, dp);
     }
+    DHIP_OK(hipGetLastError());
+  }
+  dn->last_launches = n;
+  return SRT_OK;
+}
+
+int srt_variance_abi_version(void) { return SRT_VARIANCE_ABI_VERSION; }
+
+int srt_denoise_enable_variance(srt_denoiser* dn) {
+  if (!dn) return SRT_ERR_INVALID;
+  if (dn->d_var[0]) return SRT_OK;
+  DHIP_OK(hipSetDevice(dn->device));
+  float* v[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    const hipError_t e = hipMalloc(&v[k], srt::denoise::VarianceBytes(dn->sizes));
+    if (e != hipSuccess) {
+      if (v[0]) (void)hipFree(v[0]);
+      srt::SetError(std::string("srt_denoise_enable_variance: hipMalloc: ") + hipGetErrorString(e));
+      return SRT_ERR_HIP;
+    }
+  }
+  dn->d_var[0] = v[0];
+  dn->d_var[1] = v[1];
+  return SRT_OK;
+}
+
+int srt_denoise_get_var_params(srt_denoiser* dn, srt_denoise_var_params* p) {
+  if (!dn || !p) return SRT_ERR_INVALID;
+  *p = dn->var_params;
+  return SRT_OK;
+}
+
+int srt_denoise_set_var_params(srt_denoiser* dn, const srt_denoise_var_params* p) {
+  if (int rc = srt::denoise::ValidateVarParams(p)) {  // before the object is looked at
+    srt::SetError("srt_denoise_set_var_params: sigma_lum finite and > 0, min_history 1..65535");
+    return rc;
+  }
+  if (!dn) {
+    srt::SetError("srt_denoise_set_var_params: NULL object");
+    return SRT_ERR_INVALID;
+  }
+  dn->var_params = *p;
+  return SRT_OK;
+}
+
+int srt_denoise_run_variance(srt_denoiser* dn, const void* colour_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                             const void* moments_dev, void* out_rgba32f_dev, void* out_rgba8_dev, void* out_var_f32_dev) {
+  if (!dn || !colour_rgba32f_dev || !guide_dev || !moments_dev || frames < 1 || (!out_rgba32f_dev && !out_rgba8_dev))
+    return SRT_ERR_INVALID;
+  if (!dn->d_var[0]) {
+    srt::SetError("srt_denoise_run_variance: call srt_denoise_enable_variance first");
+    return SRT_ERR_INVALID;
+  }
+  if (((uintptr_t)colour_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)moments_dev & 15u) ||
+      ((uintptr_t)out_rgba32f_dev & 15u) || ((uintptr_t)out_rgba8_dev & 3u) || ((uintptr_t)out_var_f32_dev & 3u)) {
+    srt::SetError("srt_denoise_run_variance: colour, guide, moments and out_rgba32f must be 16-byte aligned, out_rgba8 and out_var 4-byte");
+    return SRT_ERR_INVALID;
+  }
+  srt::denoise::VarLaunch sched[SRT_DENOISE_MAX_PASSES + 1];
+  const int n = srt::denoise::BuildVarianceSchedule(dn->params, dn->width, dn->height, sched);
+  if (n == 0) {
+    srt::SetError("srt_denoise_run_variance: passes must be at least 1");
+    return SRT_ERR_INVALID;
+  }
+  DHIP_OK(hipSetDevice(dn->device));
+  srt::denoise::VParams vp;
+  std::memset(&vp, 0, sizeof vp);
+  vp.hits = reinterpret_cast<const uint4*>(guide_dev);
+  vp.moments = static_cast<const float4*>(moments_dev);
+  vp.guide = dn->d_guide;
+  vp.W = dn->width;
+  vp.H = dn->height;
+  vp.nsq = (int)dn->params.normal_squarings;
+  vp.frames = (float)frames;
+  vp.sigma_d = dn->params.sigma_depth;
+  vp.sigma_l = dn->var_params.sigma_lum;
+  vp.min_history = (float)dn->var_params.min_history;
+  for (int i = 0; i < n; ++i) {
+    const srt::denoise::VarLaunch& l = sched[i];
+    vp.src = l.resolve ? static_cast<const float4*>(colour_rgba32f_dev) : dn->d_color[l.src];
+    vp.vsrc = l.resolve ? nullptr : dn->d_var[l.src];
+    vp.dst = l.last ? nullptr : dn->d_color[l.dst];
+    vp.vdst = l.last ? nullptr : dn->d_var[l.dst];
+    vp.out32 = l.last ? static_cast<float4*>(out_rgba32f_dev) : nullptr;
+    vp.out8 = l.last ? static_cast<uint32_t*>(out_rgba8_dev) : nullptr;
+    vp.outv = l.last ? static_cast<float*>(out_var_f32_dev) : nullptr;
+    vp.step = l.step;
+    const dim3 grid(l.grid_x, l.grid_y);
+    if (l.resolve)
+      hipLaunchKernelGGL(srt::denoise::variance_resolve_kernel, grid, dim3(kBlock), 0, dn->stream, vp);
+    else
+      hipLaunchKernelGGL(srt::denoise::variance_pass_kernel, grid, dim3(kBlock), 0, dn->stream, vp);
     DHIP_OK(hipGetLastError());
   }
   dn->last_launches = n;

@@ -197,6 +197,169 @@ __global__ __launch_bounds__(kBlock) void denoise_resolve_kernel(DParams dp) {
   store_px<false>(dp, i, p, o);
 }
 
+// ---- the variance-guided filter (include/srt_variance.h) ----
+//
+// 1 + passes launches, all of denoise_direct_kernel's shape: a wave covers 64 contiguous pixels of a row, colour | id
+// and normal | t are whole dwordx4 loads and the variance is a dword of an array of its own.
+//   variance_resolve_kernel  mean, guide pack and var_0: the temporal variance where the history is long enough,
+//                            else a 7 x 7 estimate from the neighbours' moments (three 16-B loads a tap, taken only
+//                            by the lanes of young pixels)
+//   variance_pass_kernel     one a-trous pass: the 3 x 3 blur of the variance (per neighbour the variance and the id,
+//                            a dword each), then the 25 taps with one more dword each; one square root and one more
+//                            division per pixel
+struct VParams {
+  const float4* src;      // resolve: the colour sum; pass: colour | id of the previous launch
+  const uint4* hits;      // resolve: the srt_hit records, 2 uint4 each
+  const float4* moments;  // resolve: (m1, m2, v, N)
+  float4* guide;          // normal | t: written by the resolve, read by the passes
+  float4* dst;            // colour | id for the next launch (nullptr in the last pass)
+  float4* out32;          // last pass: (colour, 1) or nullptr
+  uint32_t* out8;         // last pass: sRGB8 or nullptr
+  const float* vsrc;      // pass: var_i
+  float* vdst;            // var_{i+1} for the next launch, var_0 from the resolve (nullptr in the last pass)
+  float* outv;            // last pass: var_passes or nullptr
+  int W, H, step;
+  int nsq;
+  float frames;           // resolve: float(frames)
+  float sigma_d, sigma_l;
+  float min_history;      // resolve: float(min_history)
+};
+
+__device__ __forceinline__ float lum3(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
+__device__ __forceinline__ float weight_n(const VParams& vp, const float4& gp, const float4& gq) {
+  const float dot = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
+  float wn = dot > 0.0f ? dot : 0.0f;
+  for (int i = 0; i < vp.nsq; ++i) wn = wn * wn;
+  return wn;
+}
+__device__ __forceinline__ float weight_z(const VParams& vp, const float4& gp, const float4& gq) {
+  const float xz = __builtin_fabsf(gp.w - gq.w) / (vp.sigma_d * (gp.w + gq.w));
+  return 1.0f / ((1.0f + xz) * (1.0f + xz));
+}
+
+__global__ __launch_bounds__(kBlock) void variance_resolve_kernel(VParams vp) {
+  const int x = (int)blockIdx.x * kDirectW + ((int)threadIdx.x & (kDirectW - 1));
+  const int y = (int)blockIdx.y * kDirectH + (int)threadIdx.x / kDirectW;
+  if (x >= vp.W || y >= vp.H) return;
+  const int pi = y * vp.W + x;
+  const float4 a = ld16(vp.src + pi);
+  const uint4 h0 = ld16(vp.hits + 2 * (size_t)pi), h1 = ld16(vp.hits + 2 * (size_t)pi + 1);
+  const float4 m = ld16(vp.moments + pi);
+  const f3 o = mk(a.x, a.y, a.z) / vp.frames;
+  const uint32_t id = h0.x == kMissId ? kMissId : h1.z;
+  const float4 gp = make_float4(__uint_as_float(h0.z), __uint_as_float(h0.w), __uint_as_float(h1.x), __uint_as_float(h0.y));
+  float var = 0.0f;
+  if (id != kMissId) {
+    if (m.w >= vp.min_history) {
+      var = m.z;
+    } else {
+      float s1 = 0.0f, s2 = 0.0f, sw = 0.0f;
+      for (int dy = -3; dy <= 3; ++dy) {
+        const int qy = y + dy;
+        for (int dx = -3; dx <= 3; ++dx) {
+          const int qx = x + dx;
+          if (qx < 0 || qx >= vp.W || qy < 0 || qy >= vp.H) continue;
+          const int qi = qy * vp.W + qx;
+          const uint4 q0 = ld16(vp.hits + 2 * (size_t)qi), q1 = ld16(vp.hits + 2 * (size_t)qi + 1);
+          const float4 mq = ld16(vp.moments + qi);
+          if ((q0.x == kMissId ? kMissId : q1.z) != id || !finite1(mq.x) || !finite1(mq.y)) continue;
+          const float4 gq = make_float4(__uint_as_float(q0.z), __uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q0.y));
+          const float w = weight_n(vp, gp, gq) * weight_z(vp, gp, gq);
+          s1 += w * mq.x;
+          s2 += w * mq.y;
+          sw += w;
+        }
+      }
+      if (sw > 0.0f) {
+        const float ea = s1 / sw, eb = s2 / sw;
+        const float d = eb - ea * ea;
+        var = (d > 0.0f ? d : 0.0f) * (vp.min_history / m.w);
+      }
+    }
+  }
+  vp.guide[pi] = gp;
+  vp.dst[pi] = make_float4(o.x, o.y, o.z, __uint_as_float(id));
+  vp.vdst[pi] = var;
+}
+
+__global__ __launch_bounds__(kBlock) void variance_pass_kernel(VParams vp) {
+  const int x = (int)blockIdx.x * kDirectW + ((int)threadIdx.x & (kDirectW - 1));
+  const int y = (int)blockIdx.y * kDirectH + (int)threadIdx.x / kDirectW;
+  if (x >= vp.W || y >= vp.H) return;
+  const int pi = y * vp.W + x;
+  Px p;
+  p.c = ld16(vp.src + pi);
+  p.g = ld16(vp.guide + pi);
+  f3 c = mk(p.c.x, p.c.y, p.c.z);
+  float var = 0.0f;
+  if (px_id(p.c) != kMissId) {
+    var = vp.vsrc[pi];
+    // the variance blurred over the 3 x 3 neighbours, whatever the step
+    float sg = 0.0f, sk = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+      const int qy = y + dy;
+#pragma unroll
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int qx = x + dx;
+        if (qx < 0 || qx >= vp.W || qy < 0 || qy >= vp.H) continue;
+        const int qi = qy * vp.W + qx;
+        const uint32_t qid = __float_as_uint(reinterpret_cast<const float*>(vp.src + qi)[3]);
+        const float vq = vp.vsrc[qi];
+        if (qid != px_id(p.c) || !finite1(vq)) continue;
+        const float kg = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+        sg += kg * vq;
+        sk += kg;
+      }
+    }
+    const float g = sk > 0.0f ? sg / sk : 0.0f;
+    const float sl = vp.sigma_l * __builtin_sqrtf(g) + 1e-4f;
+    const float Lp = lum3(p.c.x, p.c.y, p.c.z);
+    const bool lfin = finite1(Lp);
+    float sw = 0.0f, sv = 0.0f;
+    f3 sum = mk(0.0f, 0.0f, 0.0f);
+    const int s = vp.step;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+      const int qy = y + dy * s;
+#pragma unroll
+      for (int dx = -2; dx <= 2; ++dx) {
+        const int qx = x + dx * s;
+        if (qx < 0 || qx >= vp.W || qy < 0 || qy >= vp.H) continue;
+        const int qi = qy * vp.W + qx;
+        const float4 cq = ld16(vp.src + qi), gq = ld16(vp.guide + qi);
+        const float vq = vp.vsrc[qi];
+        if (px_id(cq) != px_id(p.c) || !finite3(cq)) continue;
+        float wl = 1.0f;
+        if (lfin) {
+          const float xl = __builtin_fabsf(Lp - lum3(cq.x, cq.y, cq.z)) / sl;
+          wl = 1.0f / ((1.0f + xl) * (1.0f + xl));
+        }
+        const float w = (((tap_h(dx) * tap_h(dy)) * weight_n(vp, p.g, gq)) * weight_z(vp, p.g, gq)) * wl;
+        if (!(w > 0.0f)) continue;
+        sw += w;
+        sum.x += w * cq.x;
+        sum.y += w * cq.y;
+        sum.z += w * cq.z;
+        if (finite1(vq)) sv += (w * w) * vq;
+      }
+    }
+    if (sw > 0.0f) {
+      c = mk(sum.x / sw, sum.y / sw, sum.z / sw);
+      var = sv / (sw * sw);
+    }
+  }
+  if (vp.dst) vp.dst[pi] = make_float4(c.x, c.y, c.z, p.c.w);
+  if (vp.vdst) vp.vdst[pi] = var;
+  if (vp.out32) vp.out32[pi] = make_float4(c.x, c.y, c.z, 1.0f);
+  if (vp.out8) {
+    const uint32_t r = to_unorm8(linearToSrgb(c.x)), g = to_unorm8(linearToSrgb(c.y)), b = to_unorm8(linearToSrgb(c.z));
+    vp.out8[pi] = r | (g << 8) | (b << 16) | (255u << 24);
+  }
+  if (vp.outv) vp.outv[pi] = var;
+}
+
 struct RayParams {
   float4* rays;  // 2 float4 per srt_ray: origin | pad0, direction | intersection_distance
   int W, H;

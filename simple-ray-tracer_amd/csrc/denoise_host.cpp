@@ -73,6 +73,39 @@ int BuildSchedule(const srt_denoise_params& p, int tile_max_step, int width, int
   return n;
 }
 
+srt_denoise_var_params DefaultVarParams() {
+  // sigma_lum: the lowest tone-mapped MSE of tools/variance_sigma_grid.py's grid at 5 passes, summed over its two
+  // sequences ("Variance-guided filter"); SVGF's own 4 was the starting point
+  srt_denoise_var_params p;
+  p.sigma_lum = 1.0f;
+  p.min_history = 4;
+  return p;
+}
+
+int ValidateVarParams(const srt_denoise_var_params* p) {
+  if (!p) return SRT_ERR_INVALID;
+  if (!std::isfinite(p->sigma_lum) || !(p->sigma_lum > 0.0f)) return SRT_ERR_INVALID;
+  if (p->min_history < 1 || p->min_history > (uint32_t)SRT_VARIANCE_MAX_MIN_HISTORY) return SRT_ERR_INVALID;
+  return SRT_OK;
+}
+
+int BuildVarianceSchedule(const srt_denoise_params& p, int width, int height, VarLaunch out[SRT_DENOISE_MAX_PASSES + 1]) {
+  const int n = (int)(p.passes < (uint32_t)SRT_DENOISE_MAX_PASSES ? p.passes : (uint32_t)SRT_DENOISE_MAX_PASSES);
+  if (n == 0) return 0;
+  for (int l = 0; l <= n; ++l) {
+    VarLaunch& q = out[l];
+    q = VarLaunch();
+    q.resolve = l == 0;
+    q.last = l == n;
+    q.step = l == 0 ? 0 : 1 << (l - 1);
+    q.src = l == 0 ? kAccum : ((l - 1) & 1);
+    q.dst = q.last ? kOutput : (l & 1);
+    q.grid_x = (unsigned)((width + kDirectW - 1) / kDirectW);
+    q.grid_y = (unsigned)((height + kDirectH - 1) / kDirectH);
+  }
+  return n + 1;
+}
+
 void PrimaryBasis(const float origin[3], const float front[3], const float right[3], const float up[3], int width,
                   int height, Basis* out) {
   const float w = (float)width, h = (float)height;

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/srt_denoise.h"
+#include "../../include/srt_variance.h"
 
 namespace srt {
 namespace denoise {
@@ -64,6 +65,27 @@ struct Pass {
 // Fills out[0 .. passes - 1] and returns `passes`.
 int BuildSchedule(const srt_denoise_params& p, int tile_max_step, int width, int height,
                   Pass out[SRT_DENOISE_MAX_PASSES]);
+
+// ---- the variance-guided filter (include/srt_variance.h) ----
+
+srt_denoise_var_params DefaultVarParams();
+// SRT_OK, or SRT_ERR_INVALID: NULL, sigma_lum not finite and > 0, min_history outside 1..65535.
+int ValidateVarParams(const srt_denoise_var_params* p);
+// One variance array: a float per pixel.  The object holds two; they are no part of Sizes::scratch_bytes.
+inline size_t VarianceBytes(const Sizes& s) { return (size_t)s.pixels * 4; }
+
+// A launch of srt_denoise_run_variance.  Launch 0 is the resolve (mean, guide pack, var_0) into set 0 of the
+// ping-pong colour and variance buffers; launch 1 + i is pass i, reading set i & 1 and writing the other, the
+// last one the outputs.  Every launch has the direct kernel's shape (kDirectW x kDirectH pixels a block).
+struct VarLaunch {
+  bool resolve = false;
+  bool last = false;
+  int step = 0;            // 2^i (0 for the resolve)
+  int src = kAccum, dst = kOutput;
+  unsigned grid_x = 0, grid_y = 0;
+};
+// Fills out[0 .. passes] and returns 1 + passes, or 0 when passes == 0 (the variance filter needs a pass).
+int BuildVarianceSchedule(const srt_denoise_params& p, int width, int height, VarLaunch out[SRT_DENOISE_MAX_PASSES + 1]);
 
 // du = right / W, dv = up / H, p00 = (o + front - right/2 - up/2) + 0.5 * (du + dv); fp32, in that order.
 struct Basis {

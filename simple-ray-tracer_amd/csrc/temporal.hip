@@ -8,6 +8,7 @@
 
 #include "../../include/srt_temporal.h"
 #include "../../include/srt_temporal_motion.h"
+#include "../../include/srt_variance.h"
 #include "denoise_host.hpp"
 #include "srt_internal.hpp"
 #include "temporal.hpp"
@@ -36,6 +37,8 @@ struct srt_temporal {
   srt::temporal::Poses poses;
   uint4* d_motion = nullptr;      // one MotionRecord per BVH record; grown by srt_temporal_set_models only
   uint32_t motion_capacity = 0;   // records
+  float2* d_moments[2] = {nullptr, nullptr};  // m1 | m2 (include/srt_variance.h); allocated by srt_temporal_enable_moments
+  srt::temporal::Moments moments;
   int last_launches = 0;
 };
 
@@ -46,6 +49,7 @@ void FreeAll(srt_temporal* tp) {
     if (tp->d_color[k]) (void)hipFree(tp->d_color[k]);
     if (tp->d_guide[k]) (void)hipFree(tp->d_guide[k]);
     if (tp->d_id[k]) (void)hipFree(tp->d_id[k]);
+    if (tp->d_moments[k]) (void)hipFree(tp->d_moments[k]);
   }
   if (tp->d_motion) (void)hipFree(tp->d_motion);
   if (tp->own_stream && tp->stream) (void)hipStreamDestroy(tp->stream);
@@ -119,6 +123,10 @@ int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
   else if (n == "launches") *v = tp->last_launches;
   else if (n == "models") *v = (int)tp->poses.cur.size();
   else if (n == "models.bytes") *v = (int)(tp->motion_capacity * sizeof(srt::temporal::MotionRecord));
+  else if (n == "moments.bytes") {
+    const size_t b = tp->moments.enabled ? 2 * srt::temporal::MomentBytes(tp->sizes) : 0;
+    *v = (int)(b < 0x7FFFFFFFu ? b : 0x7FFFFFFFu);
+  }
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -143,11 +151,17 @@ int srt_temporal_reset(srt_temporal* tp) {
   if (!tp) return SRT_ERR_INVALID;
   srt::temporal::Reset(&tp->hist);
   srt::temporal::ResetPoses(&tp->poses);
+  srt::temporal::ResetMoments(&tp->moments);
   return SRT_OK;
 }
 
-int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
-                            const srt_temporal_camera* cam, void* out_rgba32f_dev) {
+}  // extern "C"
+
+namespace {
+
+// Both accumulate functions: out_moments_dev is NULL for srt_temporal_accumulate.
+int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+               const srt_temporal_camera* cam, void* out_rgba32f_dev, void* out_moments_dev) {
   if (!tp || !accum_rgba32f_dev || !guide_dev || !cam || !out_rgba32f_dev || frames < 1) return SRT_ERR_INVALID;
   if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u)) {
     srt::SetError("srt_temporal_accumulate: accum, guide and out must be 16-byte aligned");
@@ -189,9 +203,21 @@ int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int
   std::memcpy(kp.pf, pc.front, sizeof kp.pf);
   std::memcpy(kp.pr, pc.right, sizeof kp.pr);
   std::memcpy(kp.pu, pc.up, sizeof kp.pu);
+  MParams mp;
+  std::memset(&mp, 0, sizeof mp);
+  if (out_moments_dev) {
+    mp.pm = tp->d_moments[rd];
+    mp.nm = tp->d_moments[wr];
+    mp.out = static_cast<float4*>(out_moments_dev);
+    mp.has_prev = MomentsHavePrev(tp->moments, tp->hist);
+  }
   const uint32_t n = (uint32_t)tp->poses.cur.size();  // <= motion_capacity: srt_temporal_set_models grew the array
+  const dim3 grid(tp->sizes.grid_x, tp->sizes.grid_y);
   if (n == 0) {
-    hipLaunchKernelGGL(temporal_accumulate_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream, kp);
+    if (out_moments_dev)
+      hipLaunchKernelGGL(temporal_accumulate_moments_kernel, grid, dim3(kBlock), 0, tp->stream, kp, mp);
+    else
+      hipLaunchKernelGGL(temporal_accumulate_kernel, grid, dim3(kBlock), 0, tp->stream, kp);
   } else {
     // The records travel in kernel arguments, which the launch copies before it returns; stream order puts them
     // behind the previous frame's kernel, so one device array serves.
@@ -200,14 +226,61 @@ int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int
       const uint32_t count = FillChunk(tp->poses, first, &chunk);
       hipLaunchKernelGGL(temporal_motion_upload_kernel, dim3(1), dim3(kUploadLanes), 0, tp->stream, chunk, tp->d_motion, first, count);
     }
-    hipLaunchKernelGGL(temporal_accumulate_motion_kernel, dim3(tp->sizes.grid_x, tp->sizes.grid_y), dim3(kBlock), 0, tp->stream,
-                       kp, (const uint4*)tp->d_motion, n);
+    if (out_moments_dev)
+      hipLaunchKernelGGL(temporal_accumulate_motion_moments_kernel, grid, dim3(kBlock), 0, tp->stream, kp, mp,
+                         (const uint4*)tp->d_motion, n);
+    else
+      hipLaunchKernelGGL(temporal_accumulate_motion_kernel, grid, dim3(kBlock), 0, tp->stream, kp, (const uint4*)tp->d_motion, n);
   }
   THIP_OK(hipGetLastError());
   Advance(&tp->hist, *cam);
   AdvancePoses(&tp->poses);
+  AdvanceMoments(&tp->moments, out_moments_dev != nullptr);
   tp->last_launches = 1 + (int)UploadLaunches(n);
   return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                            const srt_temporal_camera* cam, void* out_rgba32f_dev) {
+  return Accumulate(tp, accum_rgba32f_dev, frames, guide_dev, cam, out_rgba32f_dev, nullptr);
+}
+
+int srt_temporal_enable_moments(srt_temporal* tp) {
+  if (!tp) return SRT_ERR_INVALID;
+  if (tp->moments.enabled) return SRT_OK;
+  THIP_OK(hipSetDevice(tp->device));
+  float2* m[2] = {nullptr, nullptr};
+  for (int k = 0; k < 2; ++k) {
+    const hipError_t e = hipMalloc(&m[k], srt::temporal::MomentBytes(tp->sizes));
+    if (e != hipSuccess) {
+      if (m[0]) (void)hipFree(m[0]);
+      srt::SetError(std::string("srt_temporal_enable_moments: hipMalloc: ") + hipGetErrorString(e));
+      return SRT_ERR_HIP;
+    }
+  }
+  tp->d_moments[0] = m[0];
+  tp->d_moments[1] = m[1];
+  srt::temporal::EnableMoments(&tp->moments);
+  return SRT_OK;
+}
+
+int srt_temporal_accumulate_moments(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                                    const srt_temporal_camera* cam, void* out_rgba32f_dev, void* out_moments_dev) {
+  if (!tp || !out_moments_dev) return SRT_ERR_INVALID;
+  if (!tp->moments.enabled) {
+    srt::SetError("srt_temporal_accumulate_moments: call srt_temporal_enable_moments first");
+    return SRT_ERR_INVALID;
+  }
+  if (((uintptr_t)out_moments_dev & 15u) || out_moments_dev == accum_rgba32f_dev || out_moments_dev == (const void*)guide_dev ||
+      out_moments_dev == out_rgba32f_dev) {
+    srt::SetError("srt_temporal_accumulate_moments: out_moments must be 16-byte aligned and alias no other pointer");
+    return SRT_ERR_INVALID;
+  }
+  return Accumulate(tp, accum_rgba32f_dev, frames, guide_dev, cam, out_rgba32f_dev, out_moments_dev);
 }
 
 int srt_temporal_motion_abi_version(void) { return SRT_TEMPORAL_MOTION_ABI_VERSION; }

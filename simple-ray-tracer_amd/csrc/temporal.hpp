@@ -17,6 +17,11 @@
 // per lane, mostly the same one across a wave) ahead of the taps and moves the surface point by M_r when the
 // record is flagged MOVING.  temporal_motion_upload_kernel writes a chunk of those records, which it receives
 // by value in its kernel arguments, with ordinary vector stores.
+//
+// Luminance moments (include/srt_variance.h): a second template parameter adds, to either instance, the moment
+// history (m1, m2) as one 8-B word per pixel.  The four extra tap loads are issued with the twelve, ahead of the
+// single wait ladder, and accumulate with the colour's weights; the two instances without moments are the code
+// they were (the additions are all under `if constexpr`).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -66,8 +71,27 @@ __device__ __forceinline__ uint4 ld16(const uint4* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-template <bool MOTION>
-__device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* __restrict__ motion, uint32_t n_motion) {
+// A whole 8-B word in one dwordx2, as ld16 above.
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float2 ld8(const float2* p) {
+  v2f v = *reinterpret_cast<const v2f*>(p);
+  asm("" : "+v"(v));
+  return make_float2(v.x, v.y);
+}
+
+// The moment history of include/srt_variance.h, next to TParams (whose layout the kernels without moments keep).
+struct MParams {
+  const float2* pm;  // previous frame: m1 | m2
+  float2* nm;        // this frame's, for the next call
+  float4* out;       // (m1, m2, v, N)
+  int has_prev;      // 0: set `pm` holds no moments of the previous frame
+};
+
+__device__ __forceinline__ float lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
+template <bool MOTION, bool MOMENTS>
+__device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* __restrict__ motion, uint32_t n_motion,
+                                                 const MParams mp) {
   const int i = (int)blockIdx.x * kRowW + ((int)threadIdx.x & (kRowW - 1));
   const int j = (int)blockIdx.y * kRowH + (int)threadIdx.x / kRowW;
   if (i >= tp.W || j >= tp.H) return;
@@ -79,6 +103,12 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
   const float t = __uint_as_float(h0.y);
   const float nx = __uint_as_float(h0.z), ny = __uint_as_float(h0.w), nz = __uint_as_float(h1.x);
   float4 res = make_float4(cx, cy, cz, 1.0f);
+  float L = 0.0f, m1 = 0.0f, m2 = 0.0f, Nm = 1.0f;
+  if constexpr (MOMENTS) {
+    L = lum(cx, cy, cz);
+    m1 = L;
+    m2 = L * L;
+  }
   if (tp.has_prev && id != kMissId) {
     const float fi = (float)i, fj = (float)j;
     const float dx = ((tp.p00[0] + fi * tp.du[0]) + fj * tp.dv[0]) - tp.o[0];
@@ -119,8 +149,9 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
         const float fu = __builtin_floorf(uu), fv = __builtin_floorf(vv);
         const int i0 = (int)fu, j0 = (int)fv;  // -1 .. W-1, -1 .. H-1
         const float fx = uu - fu, fy = vv - fv;
-        // all twelve loads first, from addresses clamped into the image
+        // all twelve loads first (sixteen with moments), from addresses clamped into the image
         float4 qc[4], qg[4];
+        float2 qm[4];
         uint32_t qid[4];
         bool inside[4];
 #pragma unroll
@@ -132,8 +163,10 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
           qid[k] = tp.pid[qi];
           qg[k] = ld16(tp.pgd + qi);
           qc[k] = ld16(tp.pcol + qi);
+          if constexpr (MOMENTS) qm[k] = ld8(mp.pm + qi);
         }
         float sw = 0.0f, smx = 0.0f, smy = 0.0f, smz = 0.0f, Nh = __builtin_inff();
+        float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {  // dy outer, dx inner
           const float wb = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
@@ -148,6 +181,10 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
             smy += wb * q.y;
             smz += wb * q.z;
             Nh = q.w < Nh ? q.w : Nh;
+            if constexpr (MOMENTS) {
+              s1 += wb * qm[k].x;
+              s2 += wb * qm[k].y;
+            }
           }
         }
         if (sw > 0.0f) {
@@ -157,8 +194,23 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
             const float N = n1 < tp.max_history ? n1 : tp.max_history;
             const float k = 1.0f / N;
             res = make_float4(hx + k * (cx - hx), hy + k * (cy - hy), hz + k * (cz - hz), N);
+            if constexpr (MOMENTS) {
+              if (mp.has_prev) {
+                const float h1 = s1 / sw, h2 = s2 / sw;
+                m1 = h1 + k * (L - h1);
+                m2 = h2 + k * (L * L - h2);
+                Nm = N;
+              }
+            }
           } else {
             res = make_float4(hx, hy, hz, Nh);  // a NaN sample: repaired from the history, not counted
+            if constexpr (MOMENTS) {
+              if (mp.has_prev) {
+                m1 = s1 / sw;
+                m2 = s2 / sw;
+                Nm = Nh;
+              }
+            }
           }
         }
       }
@@ -168,16 +220,32 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
   tp.ncol[pi] = res;
   tp.ngd[pi] = make_float4(nx, ny, nz, t);
   tp.nid[pi] = id;
+  if constexpr (MOMENTS) {
+    const float d = m2 - m1 * m1;
+    mp.nm[pi] = make_float2(m1, m2);
+    mp.out[pi] = make_float4(m1, m2, d > 0.0f ? d : 0.0f, Nm);  // a NaN difference gives 0
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void temporal_accumulate_kernel(TParams tp) {
-  accumulate_pixel<false>(tp, nullptr, 0u);
+  accumulate_pixel<false, false>(tp, nullptr, 0u, MParams());
 }
 
 // `motion`: n_motion >= 1 MotionRecords, 64-B aligned.
 __global__ __launch_bounds__(kBlock) void temporal_accumulate_motion_kernel(TParams tp, const uint4* __restrict__ motion,
                                                                             uint32_t n_motion) {
-  accumulate_pixel<true>(tp, motion, n_motion);
+  accumulate_pixel<true, false>(tp, motion, n_motion, MParams());
+}
+
+// The same two with the luminance moments of include/srt_variance.h.
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_moments_kernel(TParams tp, MParams mp) {
+  accumulate_pixel<false, true>(tp, nullptr, 0u, mp);
+}
+
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_motion_moments_kernel(TParams tp, MParams mp,
+                                                                                    const uint4* __restrict__ motion,
+                                                                                    uint32_t n_motion) {
+  accumulate_pixel<true, true>(tp, motion, n_motion, mp);
 }
 
 // One block of kUploadLanes lanes: lane k stores 16-B word k of the chunk, records [first, first + count) of `dst`

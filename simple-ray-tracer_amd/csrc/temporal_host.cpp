@@ -149,5 +149,21 @@ void ResetPoses(Poses* p) {
   p->prev.clear();
 }
 
+// ---- luminance moments ----
+
+void EnableMoments(Moments* m) {
+  if (m->enabled) return;
+  m->enabled = true;
+  m->valid = false;
+}
+
+void AdvanceMoments(Moments* m, bool with_moments) {
+  m->valid = m->enabled && with_moments;
+}
+
+void ResetMoments(Moments* m) {
+  m->valid = false;
+}
+
 }  // namespace temporal
 }  // namespace srt

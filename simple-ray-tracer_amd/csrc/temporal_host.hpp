@@ -89,5 +89,23 @@ inline uint32_t UploadLaunches(uint32_t n) { return (n + kUploadChunk - 1) / kUp
 void AdvancePoses(Poses* p);
 void ResetPoses(Poses* p);
 
+// ---- luminance moments (include/srt_variance.h) ----
+
+// One moment array: float2 (m1 | m2) per pixel.  The object holds two, indexed as the colour history's sets are
+// (History::read and WriteIndex), and they are no part of Sizes::scratch_bytes.
+inline size_t MomentBytes(const Sizes& s) { return (size_t)s.pixels * 8; }
+// Whether the arrays exist and whether set History::read holds the moments of the previous frame.
+struct Moments {
+  bool enabled = false;
+  bool valid = false;
+};
+// srt_temporal_enable_moments: idempotent; a history that existed before has no moments.
+void EnableMoments(Moments* m);
+// 1 when the call about to be enqueued finds moments of the previous frame (and a colour history to go with them).
+inline int MomentsHavePrev(const Moments& m, const History& h) { return m.enabled && m.valid && h.valid ? 1 : 0; }
+// After a call was enqueued: `with_moments` tells which of the two accumulate functions it was.
+void AdvanceMoments(Moments* m, bool with_moments);
+void ResetMoments(Moments* m);
+
 }  // namespace temporal
 }  // namespace srt

@@ -262,6 +262,25 @@ _TEMPORAL_MOTION_SIGS = {
 }
 TEMPORAL_MOTION_SYMBOLS = tuple(_TEMPORAL_MOTION_SIGS)
 
+
+
+class DenoiseVarParams(C.Structure):
+    """srt_denoise_var_params (include/srt_variance.h)."""
+    _fields_ = [("sigma_lum", C.c_float), ("min_history", C.c_uint32)]
+
+
+# include/srt_variance.h: temporal luminance moments and the variance-guided filter (its own header and version)
+_VARIANCE_SIGS = {
+    "srt_variance_abi_version": (C.c_int, []),
+    "srt_temporal_enable_moments": (C.c_int, [P]),
+    "srt_temporal_accumulate_moments": (C.c_int, [P, P, C.c_int, P, C.POINTER(TemporalCamera), P, P]),
+    "srt_denoise_enable_variance": (C.c_int, [P]),
+    "srt_denoise_get_var_params": (C.c_int, [P, C.POINTER(DenoiseVarParams)]),
+    "srt_denoise_set_var_params": (C.c_int, [P, C.POINTER(DenoiseVarParams)]),
+    "srt_denoise_run_variance": (C.c_int, [P, P, C.c_int, P, P, P, P, P]),
+}
+VARIANCE_SYMBOLS = tuple(_VARIANCE_SIGS)
+
 _lib = None
 
 
@@ -294,7 +313,7 @@ def lib() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
-                                  + list(_TEMPORAL_MOTION_SIGS.items())):
+                                  + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import DenoiseParams, check, lib
+from ._lib import DenoiseParams, DenoiseVarParams, check, lib
 
 __all__ = ["Denoiser"]
 
@@ -137,6 +137,56 @@ class Denoiser:
                                                 C.c_void_p(out8.data_ptr()) if srgb else None), "srt_denoise_run")
         del keep
         return (out, out8) if srgb else out
+
+    # -- the variance-guided filter (include/srt_variance.h) --------------------
+    def enable_variance(self):
+        """Allocate the ping-pong variance arrays; idempotent."""
+        check(lib().srt_denoise_enable_variance(self.handle), "srt_denoise_enable_variance")
+
+    @property
+    def variance_params(self) -> dict:
+        p = DenoiseVarParams()
+        check(lib().srt_denoise_get_var_params(self.handle, C.byref(p)), "srt_denoise_get_var_params")
+        return {n: getattr(p, n) for n, _ in DenoiseVarParams._fields_}
+
+    def set_variance_params(self, **kw):
+        """Any of sigma_lum, min_history; the other keeps its value."""
+        cur = self.variance_params
+        unknown = set(kw) - set(cur)
+        if unknown:
+            raise TypeError(f"unknown variance parameter(s): {sorted(unknown)}")
+        cur.update(kw)
+        mh = int(cur["min_history"])
+        if not 0 <= mh <= 0xFFFFFFFF:
+            raise ValueError("min_history must fit an unsigned 32-bit integer")
+        p = DenoiseVarParams(float(cur["sigma_lum"]), mh)
+        check(lib().srt_denoise_set_var_params(self.handle, C.byref(p)), "srt_denoise_set_var_params")
+
+    def run_variance(self, colour, frames: int, hits, moments, *, srgb: bool = False):
+        """The variance-guided filter: ``colour`` (the SUM over ``frames``; ``Temporal.accumulate_moments``' ``out``
+        with ``frames`` = 1) and ``moments`` are contiguous float32 ``[H, W, 4]`` device tensors, ``hits`` the guide.
+        Uses ``passes`` (at least 1), ``normal_squarings`` and ``sigma_depth`` of ``params`` and ``variance_params``.
+        Returns ``(out, variance)``: the float32 ``[H, W, 4]`` result and the float32 ``[H, W]`` variance left after
+        the last pass; with ``srgb=True`` ``(out, out8, variance)``.  Needs ``enable_variance()``."""
+        import torch
+        dev = f"cuda:{self.device}"
+        for name, t in (("colour", colour), ("moments", moments)):
+            if (t.dtype != torch.float32 or not t.is_cuda or t.device.index != self.device
+                    or not t.is_contiguous() or t.numel() != self.width * self.height * 4):
+                raise ValueError(f"{name} must be a contiguous float32 [H, W, 4] tensor on {dev}")
+        raw = getattr(hits, "raw", hits)
+        if raw is None or (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device
+                           or not raw.is_contiguous() or tuple(raw.shape) != (self.width * self.height, 8)):
+            raise ValueError(f"hits must be the [W * H, 8] int32 srt_hit tensor on {dev}")
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        out8 = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=dev) if srgb else None
+        var = torch.empty((self.height, self.width), dtype=torch.float32, device=dev)
+        self._run(lambda: lib().srt_denoise_run_variance(self.handle, C.c_void_p(colour.data_ptr()), int(frames),
+                                                         C.c_void_p(raw.data_ptr()), C.c_void_p(moments.data_ptr()),
+                                                         C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(out8.data_ptr()) if srgb else None,
+                                                         C.c_void_p(var.data_ptr())), "srt_denoise_run_variance")
+        return (out, out8, var) if srgb else (out, var)
 
     def synchronize(self):
         """Wait for the work enqueued so far."""

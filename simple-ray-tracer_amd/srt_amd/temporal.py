@@ -168,6 +168,37 @@ class Temporal:
         del keep
         return out
 
+    def enable_moments(self):
+        """Allocate the luminance-moment history (include/srt_variance.h); idempotent."""
+        check(lib().srt_temporal_enable_moments(self.handle), "srt_temporal_enable_moments")
+
+    def accumulate_moments(self, accum, frames: int, hits, camera):
+        """``accumulate``, and the per-pixel luminance moments: returns ``(out, moments)``, ``out`` bit for bit what
+        ``accumulate`` returns and ``moments`` a float32 ``[H, W, 4]`` device tensor ``(m1, m2, variance, N)`` for
+        ``Denoiser.run_variance``.  Needs ``enable_moments()``."""
+        import torch
+        dev = f"cuda:{self.device}"
+        if isinstance(accum, int):
+            acc_ptr, keep = accum, None
+        else:
+            if (accum.dtype != torch.float32 or not accum.is_cuda or accum.device.index != self.device
+                    or not accum.is_contiguous() or accum.numel() != self.width * self.height * 4):
+                raise ValueError(f"accum must be a contiguous float32 [H, W, 4] tensor on {dev}")
+            acc_ptr, keep = accum.data_ptr(), accum
+        raw = getattr(hits, "raw", hits)
+        if raw is None or (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device
+                           or not raw.is_contiguous() or tuple(raw.shape) != (self.width * self.height, 8)):
+            raise ValueError(f"hits must be the [W * H, 8] int32 srt_hit tensor on {dev}")
+        cam = _camera(camera)
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        mom = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        self._run(lambda: lib().srt_temporal_accumulate_moments(self.handle, C.c_void_p(acc_ptr), int(frames),
+                                                                C.c_void_p(raw.data_ptr()), C.byref(cam),
+                                                                C.c_void_p(out.data_ptr()), C.c_void_p(mom.data_ptr())),
+                  "srt_temporal_accumulate_moments")
+        del keep
+        return out, mom
+
     def synchronize(self):
         """Wait for the work enqueued so far."""
         import torch

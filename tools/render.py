@@ -1,7 +1,7 @@
 """Render a scene to an image file on the GPU: the reference's progressive loop, headless.
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
-                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K] [--spin DEG]
+                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K] [--spin DEG] [--variance]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -37,7 +37,13 @@ def main():
                     help="with --orbit K: the camera stands still and the first model turns by DEG degrees per frame "
                          "about the vertical axis through its bounds' centre; each frame's matrix goes to the renderer, "
                          "the query and the temporal object, whose history follows the model")
+    ap.add_argument("--variance", action="store_true",
+                    help="with --orbit K (and --spin): the temporal object also integrates luminance moments, and the "
+                         "last frame is written a fourth way, <out>_svgf: temporally accumulated, then through the "
+                         "variance-guided filter (include/srt_variance.h)")
     a = ap.parse_args()
+    if a.variance and not a.orbit:
+        ap.error("--variance needs --orbit K")
     if a.spin and not a.orbit:
         ap.error("--spin DEG needs --orbit K")
     if a.orbit and a.scene == "spheres":
@@ -62,12 +68,12 @@ def main():
     if a.orbit:
         try:
             t0 = time.perf_counter()
-            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin)
+            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance)
             dt = time.perf_counter() - t0
         finally:
             r.close()
         print(f"{a.orbit} frames of {a.width}x{a.height} @ {a.spp} spp in {dt:.3f} s; the last one:")
-        for what, p in zip(("raw", "denoised", "temporal + denoised"), paths):
+        for what, p in zip(("raw", "denoised", "temporal + denoised", "temporal + variance-guided filter"), paths):
             print(f"{p}: {what}")
         return
     try:
@@ -126,22 +132,26 @@ def spin_frame(scene, degrees):
     return m.T.reshape(16).astype(np.float32)
 
 
-def orbit(r, setup, frames, spp, out, spin=0.0):
+def orbit(r, setup, frames, spp, out, spin=0.0, variance=False):
     """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
     (degrees per frame) under a still camera while the first model turns.  Every frame goes through
     srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame raw,
-    denoised, and temporally accumulated then denoised; returns the three paths."""
+    denoised, and temporally accumulated then denoised, and with `variance` also temporally accumulated then through
+    the variance-guided filter (<out>_svgf); returns the paths."""
     import srt_amd as S
     from srt_amd.denoise import Denoiser
     from srt_amd.query import Query
     from srt_amd.temporal import Temporal
 
     out = pathlib.Path(out)
-    paths = [out] + [out.with_name(out.stem + s + out.suffix) for s in ("_denoised", "_temporal")]
+    paths = [out] + [out.with_name(out.stem + s + out.suffix) for s in ("_denoised", "_temporal") + (("_svgf",) if variance else ())]
     cam, c = setup.camera, r.compute
     acc_ptr, _ = c.image_pointers()
     with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, Query(setup.scene) as q:
         q.set_bvh_count(setup.bvh_count)
+        if variance:
+            tp.enable_moments()
+            dn.enable_variance()
         for k in range(frames):
             if spin:  # the three per-frame calls of a moving model
                 frame = spin_frame(setup.scene, spin * (k + 1))
@@ -158,13 +168,20 @@ def orbit(r, setup, frames, spp, out, spin=0.0):
             r.render(spp)  # clears first: the frame loop resets on any input
             r.finish()
             hits = q.closest(dn.primary_rays(cam))
-            acc = tp.accumulate(acc_ptr, r.accum_frames, hits, cam)
+            if variance:
+                acc, mom = tp.accumulate_moments(acc_ptr, r.accum_frames, hits, cam)
+            else:
+                acc = tp.accumulate(acc_ptr, r.accum_frames, hits, cam)
         c.save_image(paths[0])
         _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
         _, rgba8_t = dn.run(acc, 1, hits, srgb=True)
         dn.synchronize()
         S.write_image(paths[1], rgba8.cpu().numpy())
         S.write_image(paths[2], rgba8_t.cpu().numpy())
+        if variance:
+            _, rgba8_v, _ = dn.run_variance(acc, 1, hits, mom, srgb=True)
+            dn.synchronize()
+            S.write_image(paths[3], rgba8_v.cpu().numpy())
     return paths
 
 
