@@ -7,9 +7,14 @@
 #include <utility>
 
 #include "../srt_denoise.h"
+#include "../srt_surface.h"
 #include "../srt_variance.h"
 
 namespace srt {
+
+// RunAlbedo's default floor (the C ABI has none): chosen on the CPU by tools/albedo_floor_grid.py (DESIGN.md
+// section 5, "Surface attributes and demodulation").
+constexpr float kAlbedoFloor = 0.1f;
 
 class Denoiser {
  public:
@@ -61,6 +66,13 @@ class Denoiser {
     Check(srt_denoise_run_variance(d_, colour_rgba32f_dev, frames, guide_dev, moments_dev, out_rgba32f_dev, out_rgba8_dev,
                                    out_var_f32_dev),
           "srt_denoise_run_variance");
+  }
+  // Albedo-demodulated filtering (srt_surface.h): attrs_dev is Surface::shade's output for the pixel-centre rays.
+  void RunAlbedo(const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev, const srt_surface_attr* attrs_dev,
+                 void* out_rgba32f_dev, void* out_rgba8_dev, float albedo_floor = kAlbedoFloor) {
+    Check(srt_denoise_run_albedo(d_, accum_rgba32f_dev, frames, guide_dev, attrs_dev, albedo_floor, out_rgba32f_dev,
+                                 out_rgba8_dev),
+          "srt_denoise_run_albedo");
   }
   int get_int(const char* name) const {
     int v = 0;

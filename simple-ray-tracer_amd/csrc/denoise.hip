@@ -9,8 +9,10 @@
 
 #include "../../include/srt_denoise.h"
 #include "../../include/srt_variance.h"
+#include "../../include/srt_surface.h"
 #include "denoise.hpp"
 #include "denoise_host.hpp"
+#include "surface_host.hpp"
 
 #define DHIP_OK(expr)                                                         \
   do {                                                                        \
@@ -38,6 +40,7 @@ struct srt_denoiser {
 
 namespace {
 
+using srt::denoise::AParams;
 using srt::denoise::DParams;
 using srt::denoise::kBlock;
 using srt::denoise::Pass;
@@ -66,7 +69,87 @@ int Allocate(srt_denoiser* dn) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true, AParams>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false, AParams>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
+  return SRT_OK;
+}
+
+// One pass over P = DParams (srt_denoise_run, and the middle passes of srt_denoise_run_albedo) or AParams.
+template <class P>
+void LaunchPass(srt_denoiser* dn, const srt::denoise::Pass& ps, const P& dp) {
+  const dim3 grid(ps.grid_x, ps.grid_y);
+  if (ps.tiled) {
+    if (ps.first)
+      hipLaunchKernelGGL((srt::denoise::denoise_tiled_kernel<true, P>), grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
+    else
+      hipLaunchKernelGGL((srt::denoise::denoise_tiled_kernel<false, P>), grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
+  } else {
+    if (ps.first)
+      hipLaunchKernelGGL((srt::denoise::denoise_direct_kernel<true, P>), grid, dim3(kBlock), 0, dn->stream, dp);
+    else
+      hipLaunchKernelGGL((srt::denoise::denoise_direct_kernel<false, P>), grid, dim3(kBlock), 0, dn->stream, dp);
+  }
+}
+
+// srt_denoise_run (attrs == nullptr) and srt_denoise_run_albedo: the same schedule and launches; with attrs the
+// first and the last pass are the AParams instances.
+int Run(srt_denoiser* dn, const char* what, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+        const srt_surface_attr* attrs, float albedo_floor, void* out_rgba32f_dev, void* out_rgba8_dev) {
+  if (!dn || !accum_rgba32f_dev || frames < 1 || (!out_rgba32f_dev && !out_rgba8_dev)) return SRT_ERR_INVALID;
+  if (dn->params.passes > 0 && !guide_dev) {
+    srt::SetError(std::string(what) + ": a guide is needed when passes > 0");
+    return SRT_ERR_INVALID;
+  }
+  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u) ||
+      ((uintptr_t)out_rgba8_dev & 3u)) {
+    srt::SetError(std::string(what) + ": accum, guide and out_rgba32f must be 16-byte aligned, out_rgba8 4-byte");
+    return SRT_ERR_INVALID;
+  }
+  DHIP_OK(hipSetDevice(dn->device));
+  AParams dp;
+  std::memset(&dp, 0, sizeof dp);
+  dp.hits = reinterpret_cast<const uint4*>(guide_dev);
+  dp.guide = dn->d_guide;
+  dp.W = dn->width;
+  dp.H = dn->height;
+  dp.nsq = (int)dn->params.normal_squarings;
+  dp.frames = (float)frames;
+  dp.sigma_d = dn->params.sigma_depth;
+  dp.attrs = reinterpret_cast<const float4*>(attrs);
+  dp.floor = albedo_floor;
+  float4* const out32 = static_cast<float4*>(out_rgba32f_dev);
+  uint32_t* const out8 = static_cast<uint32_t*>(out_rgba8_dev);
+  Pass sched[SRT_DENOISE_MAX_PASSES];
+  const int n = srt::denoise::BuildSchedule(dn->params, dn->tile_max_step, dn->width, dn->height, sched);
+  if (n == 0) {
+    dp.src = static_cast<const float4*>(accum_rgba32f_dev);
+    dp.out32 = out32;
+    dp.out8 = out8;
+    const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(srt::denoise::denoise_resolve_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream,
+                       static_cast<const DParams&>(dp));
+    DHIP_OK(hipGetLastError());
+    dn->last_launches = 1;
+    return SRT_OK;
+  }
+  for (int i = 0; i < n; ++i) {
+    const Pass& ps = sched[i];
+    dp.src = ps.first ? static_cast<const float4*>(accum_rgba32f_dev) : dn->d_color[ps.src];
+    dp.dst = ps.last ? nullptr : dn->d_color[ps.dst];
+    dp.out32 = ps.last ? out32 : nullptr;
+    dp.out8 = ps.last ? out8 : nullptr;
+    dp.step = ps.step;
+    dp.sigma_c = ps.sigma_c;
+    if (attrs && (ps.first || ps.last))
+      LaunchPass<AParams>(dn, ps, dp);
+    else
+      LaunchPass<DParams>(dn, ps, dp);
+    DHIP_OK(hipGetLastError());
+  }
+  dn->last_launches = n;
   return SRT_OK;
 }
 
@@ -173,64 +256,24 @@ int srt_denoise_primary_rays(srt_denoiser* dn, const float origin[3], const floa
 
 int srt_denoise_run(srt_denoiser* dn, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
                     void* out_rgba32f_dev, void* out_rgba8_dev) {
-  if (!dn || !accum_rgba32f_dev || frames < 1 || (!out_rgba32f_dev && !out_rgba8_dev)) return SRT_ERR_INVALID;
-  if (dn->params.passes > 0 && !guide_dev) {
-    srt::SetError("srt_denoise_run: a guide is needed when passes > 0");
+  return Run(dn, "srt_denoise_run", accum_rgba32f_dev, frames, guide_dev, nullptr, 0.0f, out_rgba32f_dev, out_rgba8_dev);
+}
+
+int srt_denoise_run_albedo(srt_denoiser* dn, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
+                           const srt_surface_attr* attrs_dev, float albedo_floor, void* out_rgba32f_dev,
+                           void* out_rgba8_dev) {
+  if (!srt::surface::ValidFloor(albedo_floor)) {  // before the object is looked at
+    srt::SetError("srt_denoise_run_albedo: albedo_floor must be finite and > 0");
     return SRT_ERR_INVALID;
   }
-  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u) ||
-      ((uintptr_t)out_rgba8_dev & 3u)) {
-    srt::SetError("srt_denoise_run: accum, guide and out_rgba32f must be 16-byte aligned, out_rgba8 4-byte");
+  if (!dn) return SRT_ERR_INVALID;
+  if (dn->params.passes == 0) attrs_dev = nullptr;  // ignored: srt_denoise_run's result
+  else if (!attrs_dev || ((uintptr_t)attrs_dev & 15u)) {
+    srt::SetError("srt_denoise_run_albedo: attrs are needed when passes > 0, 16-byte aligned");
     return SRT_ERR_INVALID;
   }
-  DHIP_OK(hipSetDevice(dn->device));
-  DParams dp;
-  std::memset(&dp, 0, sizeof dp);
-  dp.hits = reinterpret_cast<const uint4*>(guide_dev);
-  dp.guide = dn->d_guide;
-  dp.W = dn->width;
-  dp.H = dn->height;
-  dp.nsq = (int)dn->params.normal_squarings;
-  dp.frames = (float)frames;
-  dp.sigma_d = dn->params.sigma_depth;
-  float4* const out32 = static_cast<float4*>(out_rgba32f_dev);
-  uint32_t* const out8 = static_cast<uint32_t*>(out_rgba8_dev);
-  Pass sched[SRT_DENOISE_MAX_PASSES];
-  const int n = srt::denoise::BuildSchedule(dn->params, dn->tile_max_step, dn->width, dn->height, sched);
-  if (n == 0) {
-    dp.src = static_cast<const float4*>(accum_rgba32f_dev);
-    dp.out32 = out32;
-    dp.out8 = out8;
-    const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(srt::denoise::denoise_resolve_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream, dp);
-    DHIP_OK(hipGetLastError());
-    dn->last_launches = 1;
-    return SRT_OK;
-  }
-  for (int i = 0; i < n; ++i) {
-    const Pass& ps = sched[i];
-    dp.src = ps.first ? static_cast<const float4*>(accum_rgba32f_dev) : dn->d_color[ps.src];
-    dp.dst = ps.last ? nullptr : dn->d_color[ps.dst];
-    dp.out32 = ps.last ? out32 : nullptr;
-    dp.out8 = ps.last ? out8 : nullptr;
-    dp.step = ps.step;
-    dp.sigma_c = ps.sigma_c;
-    const dim3 grid(ps.grid_x, ps.grid_y);
-    if (ps.tiled) {
-      if (ps.first)
-        hipLaunchKernelGGL(srt::denoise::denoise_tiled_kernel<true>, grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
-      else
-        hipLaunchKernelGGL(srt::denoise::denoise_tiled_kernel<false>, grid, dim3(kBlock), ps.lds_bytes, dn->stream, dp);
-    } else {
-      if (ps.first)
-        hipLaunchKernelGGL(srt::denoise::denoise_direct_kernel<true>, grid, dim3(kBlock), 0, dn->stream, dp);
-      else
-        hipLaunchKernelGGL(srt::denoise::denoise_direct_kernel<false>, grid, dim3(kBlock), 0, dn->stream, dp);
-    }
-    DHIP_OK(hipGetLastError());
-  }
-  dn->last_launches = n;
-  return SRT_OK;
+  return Run(dn, "srt_denoise_run_albedo", accum_rgba32f_dev, frames, guide_dev, attrs_dev, albedo_floor, out_rgba32f_dev,
+             out_rgba8_dev);
 }
 
 int srt_variance_abi_version(void) { return SRT_VARIANCE_ABI_VERSION; }

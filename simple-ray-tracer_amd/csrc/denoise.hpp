@@ -42,6 +42,25 @@ struct Px {
   float4 g;  // normal | t
 };
 
+// srt_denoise_run_albedo (include/srt_surface.h): the pass kernels instantiated over AParams filter radiance
+// divided by the surface albedo.  Their first pass divides the mean of a hit pixel by a = max(albedo, floor) as
+// it loads it, their last pass multiplies the filtered colour by a before it stores it; both read the
+// srt_surface_attr records directly (albedo | bary_v in the first of a record's two float4).  The instances over
+// DParams are the ones srt_denoise_run launches and read none of this.
+struct AParams : DParams {
+  const float4* attrs;  // 2 float4 per srt_surface_attr
+  float floor;          // albedo_floor
+};
+template <class P>
+constexpr bool kAlbedo = false;
+template <>
+constexpr bool kAlbedo<AParams> = true;
+
+__device__ __forceinline__ f3 albedo_of(const AParams& ap, int p) {
+  const float4 a = ap.attrs[2 * (size_t)p];
+  return mk(a.x > ap.floor ? a.x : ap.floor, a.y > ap.floor ? a.y : ap.floor, a.z > ap.floor ? a.z : ap.floor);
+}
+
 __device__ __forceinline__ uint32_t px_id(const float4& c) { return __float_as_uint(c.w); }
 __device__ __forceinline__ bool finite1(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ bool finite3(const float4& c) { return finite1(c.x) && finite1(c.y) && finite1(c.z); }
@@ -61,13 +80,19 @@ __device__ __forceinline__ uint4 ld16(const uint4* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-template <bool FIRST>
-__device__ __forceinline__ Px load_px(const DParams& dp, int p) {
+template <bool FIRST, class P = DParams>
+__device__ __forceinline__ Px load_px(const P& dp, int p) {
   Px r;
   if constexpr (FIRST) {
     const float4 a = ld16(dp.src + p);
     const uint4 h0 = ld16(dp.hits + 2 * (size_t)p), h1 = ld16(dp.hits + 2 * (size_t)p + 1);  // triangle t n.x n.y | n.z material bvh pad
-    const f3 o = mk(a.x, a.y, a.z) / dp.frames;
+    f3 o = mk(a.x, a.y, a.z) / dp.frames;
+    if constexpr (kAlbedo<P>) {
+      if (h0.x != kMissId) {
+        const f3 al = albedo_of(dp, p);
+        o = mk(o.x / al.x, o.y / al.y, o.z / al.z);
+      }
+    }
     r.c = make_float4(o.x, o.y, o.z, __uint_as_float(h0.x == kMissId ? kMissId : h1.z));
     r.g = make_float4(__uint_as_float(h0.z), __uint_as_float(h0.w), __uint_as_float(h1.x), __uint_as_float(h0.y));
   } else {
@@ -106,10 +131,13 @@ __device__ __forceinline__ f3 resolve(const Px& p, float sw, f3 sum) {
   return sw > 0.0f ? mk(sum.x / sw, sum.y / sw, sum.z / sw) : mk(p.c.x, p.c.y, p.c.z);
 }
 
-template <bool FIRST>
-__device__ __forceinline__ void store_px(const DParams& dp, int i, const Px& p, f3 c) {
+template <bool FIRST, class P = DParams>
+__device__ __forceinline__ void store_px(const P& dp, int i, const Px& p, f3 c) {
   if constexpr (FIRST) dp.guide[i] = p.g;
   if (dp.dst) dp.dst[i] = make_float4(c.x, c.y, c.z, p.c.w);
+  if constexpr (kAlbedo<P>) {
+    if (!dp.dst && px_id(p.c) != kMissId) c = c * albedo_of(dp, i);  // the last pass: radiance again
+  }
   if (dp.out32) dp.out32[i] = make_float4(c.x, c.y, c.z, 1.0f);
   if (dp.out8) {
     const uint32_t r = to_unorm8(linearToSrgb(c.x)), g = to_unorm8(linearToSrgb(c.y)), b = to_unorm8(linearToSrgb(c.z));
@@ -117,8 +145,8 @@ __device__ __forceinline__ void store_px(const DParams& dp, int i, const Px& p, 
   }
 }
 
-template <bool FIRST>
-__global__ __launch_bounds__(kBlock) void denoise_tiled_kernel(DParams dp) {
+template <bool FIRST, class P = DParams>
+__global__ __launch_bounds__(kBlock) void denoise_tiled_kernel(P dp) {
   const int s = dp.step, halo = 2 * s;
   const int sw_px = kTileW + 2 * halo, sh_px = kTileH + 2 * halo, n = sw_px * sh_px;
   float4* lc = g_smem;      // colour | id of the staged pixels, row-major
@@ -130,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void denoise_tiled_kernel(DParams dp) {
     Px q;
     q.c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kMissId));
     q.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (gx >= 0 && gx < dp.W && gy >= 0 && gy < dp.H) q = load_px<FIRST>(dp, gy * dp.W + gx);
+    if (gx >= 0 && gx < dp.W && gy >= 0 && gy < dp.H) q = load_px<FIRST, P>(dp, gy * dp.W + gx);
     lc[i] = q.c;
     lg[i] = q.g;
   }
@@ -155,16 +183,16 @@ __global__ __launch_bounds__(kBlock) void denoise_tiled_kernel(DParams dp) {
       }
     }
   }
-  store_px<FIRST>(dp, y * dp.W + x, p, resolve(p, sw, sum));
+  store_px<FIRST, P>(dp, y * dp.W + x, p, resolve(p, sw, sum));
 }
 
-template <bool FIRST>
-__global__ __launch_bounds__(kBlock) void denoise_direct_kernel(DParams dp) {
+template <bool FIRST, class P = DParams>
+__global__ __launch_bounds__(kBlock) void denoise_direct_kernel(P dp) {
   const int x = (int)blockIdx.x * kDirectW + ((int)threadIdx.x & (kDirectW - 1));
   const int y = (int)blockIdx.y * kDirectH + (int)threadIdx.x / kDirectW;
   if (x >= dp.W || y >= dp.H) return;
   const int pi = y * dp.W + x;
-  const Px p = load_px<FIRST>(dp, pi);
+  const Px p = load_px<FIRST, P>(dp, pi);
   float sw = 0.0f;
   f3 sum = mk(0.0f, 0.0f, 0.0f);
   if (px_id(p.c) != kMissId) {
@@ -177,12 +205,12 @@ __global__ __launch_bounds__(kBlock) void denoise_direct_kernel(DParams dp) {
       for (int dx = -2; dx <= 2; ++dx) {
         const int qx = x + dx * s;
         if (qx < 0 || qx >= dp.W || qy < 0 || qy >= dp.H) continue;
-        const Px q = load_px<FIRST>(dp, qy * dp.W + qx);
+        const Px q = load_px<FIRST, P>(dp, qy * dp.W + qx);
         tap(dp, p, pfin, q.c, q.g, tap_h(dx) * tap_h(dy), sw, sum);
       }
     }
   }
-  store_px<FIRST>(dp, pi, p, resolve(p, sw, sum));
+  store_px<FIRST, P>(dp, pi, p, resolve(p, sw, sum));
 }
 
 // passes == 0: the mean and the outputs alone (accumulate_kernel's output stage).

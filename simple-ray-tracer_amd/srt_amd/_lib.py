@@ -281,6 +281,32 @@ _VARIANCE_SIGS = {
 }
 VARIANCE_SYMBOLS = tuple(_VARIANCE_SIGS)
 
+
+class SurfaceAttr(C.Structure):
+    """srt_surface_attr (include/srt_surface.h)."""
+    _fields_ = [("albedo", C.c_float * 3), ("bary_v", C.c_float), ("bary_w", C.c_float), ("uv", C.c_float * 2),
+                ("hit", C.c_uint32)]
+
+
+assert C.sizeof(SurfaceAttr) == 32
+
+# include/srt_surface.h: surface attributes of query hits and albedo-demodulated denoising (its own header and version)
+_SURFACE_SIGS = {
+    "srt_surface_abi_version": (C.c_int, []),
+    "srt_surface_create": (C.c_int, [C.c_int, P, P, C.c_uint32, P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32,
+                                     C.POINTER(P)]),
+    "srt_surface_create_obj": (C.c_int, [C.c_int, P, P, C.POINTER(P)]),
+    "srt_surface_upload_textures": (C.c_int, [P, C.POINTER(Texture), C.c_uint32]),
+    "srt_surface_update_model_matrix": (C.c_int, [P, C.c_uint32, P]),
+    "srt_surface_set_bvh_count": (C.c_int, [P, C.c_uint32]),
+    "srt_surface_destroy": (C.c_int, [P]),
+    "srt_surface_stream": (P, [P]),
+    "srt_surface_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_surface_shade": (C.c_int, [P, P, P, C.c_uint32, P]),
+    "srt_denoise_run_albedo": (C.c_int, [P, P, C.c_int, P, P, C.c_float, P, P]),
+}
+SURFACE_SYMBOLS = tuple(_SURFACE_SIGS)
+
 _lib = None
 
 
@@ -313,7 +339,8 @@ def lib() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
-                                  + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())):
+                                  + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
+                                  + list(_SURFACE_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

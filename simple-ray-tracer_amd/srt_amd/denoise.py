@@ -13,7 +13,11 @@ import numpy as np
 
 from ._lib import DenoiseParams, DenoiseVarParams, check, lib
 
-__all__ = ["Denoiser"]
+__all__ = ["Denoiser", "ALBEDO_FLOOR"]
+
+# run_albedo's default floor (the C ABI has none): chosen on the CPU by tools/albedo_floor_grid.py (DESIGN.md
+# section 5, "Surface attributes and demodulation"); srt::kAlbedoFloor in include/srt/denoise.hpp is the same.
+ALBEDO_FLOOR = 0.1
 
 
 class Denoiser:
@@ -187,6 +191,39 @@ class Denoiser:
                                                          C.c_void_p(out8.data_ptr()) if srgb else None,
                                                          C.c_void_p(var.data_ptr())), "srt_denoise_run_variance")
         return (out, out8, var) if srgb else (out, var)
+
+    # -- albedo-demodulated filtering (include/srt_surface.h) -------------------
+    def run_albedo(self, accum, frames: int, hits, attrs, albedo_floor: float = ALBEDO_FLOOR, *, srgb: bool = False):
+        """``run`` on radiance divided by the surface albedo: ``attrs`` is ``Surface.shade``'s float32
+        ``[W * H, 8]`` tensor for the pixel-centre rays (may be None when passes == 0).  A hit pixel's mean is
+        divided by ``max(albedo, albedo_floor)`` before the first pass and the filtered colour multiplied by it in
+        the last; miss pixels pass through.  Same arguments and results as ``run`` otherwise."""
+        import torch
+        dev = f"cuda:{self.device}"
+        if isinstance(accum, int):
+            acc_ptr, keep = accum, None
+        else:
+            if (accum.dtype != torch.float32 or not accum.is_cuda or accum.device.index != self.device
+                    or not accum.is_contiguous() or accum.numel() != self.width * self.height * 4):
+                raise ValueError(f"accum must be a contiguous float32 [H, W, 4] tensor on {dev}")
+            acc_ptr, keep = accum.data_ptr(), accum
+        raw = getattr(hits, "raw", hits)
+        if raw is not None and (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device
+                                or not raw.is_contiguous() or tuple(raw.shape) != (self.width * self.height, 8)):
+            raise ValueError(f"hits must be the [W * H, 8] int32 srt_hit tensor on {dev}")
+        if attrs is not None and (attrs.dtype != torch.float32 or not attrs.is_cuda or attrs.device.index != self.device
+                                  or not attrs.is_contiguous() or tuple(attrs.shape) != (self.width * self.height, 8)):
+            raise ValueError(f"attrs must be the [W * H, 8] float32 srt_surface_attr tensor on {dev}")
+        out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
+        out8 = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=dev) if srgb else None
+        self._run(lambda: lib().srt_denoise_run_albedo(self.handle, C.c_void_p(acc_ptr), int(frames),
+                                                       C.c_void_p(raw.data_ptr()) if raw is not None else None,
+                                                       C.c_void_p(attrs.data_ptr()) if attrs is not None else None,
+                                                       C.c_float(albedo_floor), C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(out8.data_ptr()) if srgb else None),
+                  "srt_denoise_run_albedo")
+        del keep
+        return (out, out8) if srgb else out
 
     def synchronize(self):
         """Wait for the work enqueued so far."""

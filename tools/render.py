@@ -1,7 +1,7 @@
 """Render a scene to an image file on the GPU: the reference's progressive loop, headless.
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
-                              [--max-depth D] [--out frame.png] [--denoise] [--orbit K] [--spin DEG] [--variance]
+                              [--max-depth D] [--out frame.png] [--denoise] [--albedo] [--orbit K] [--spin DEG] [--variance]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--denoise", action="store_true",
                     help="also write <out>_denoised.<ext>: the frame through the edge-avoiding filter, guided by a "
                          "closest-hit query of the pixel-centre rays (mesh scenes; sphere pixels pass unfiltered)")
+    ap.add_argument("--albedo", action="store_true",
+                    help="with --denoise (mesh scenes): also write <out>_albedo_denoised.<ext>, the frame through the "
+                         "albedo-demodulated filter (include/srt_surface.h): srt_surface_shade of the guide, run_albedo")
     ap.add_argument("--orbit", type=int, default=0, metavar="K",
                     help="mesh scenes: render K frames of --spp each along a small fixed camera path, resetting the "
                          "accumulation per frame as the frame loop does while the camera moves, and write the last "
@@ -42,6 +45,8 @@ def main():
                          "last frame is written a fourth way, <out>_svgf: temporally accumulated, then through the "
                          "variance-guided filter (include/srt_variance.h)")
     a = ap.parse_args()
+    if a.albedo and (not a.denoise or a.orbit or a.scene == "spheres"):
+        ap.error("--albedo needs --denoise on a mesh scene, without --orbit")
     if a.variance and not a.orbit:
         ap.error("--variance needs --orbit K")
     if a.spin and not a.orbit:
@@ -83,19 +88,23 @@ def main():
         dt = time.perf_counter() - t0
         r.compute.save_image(a.out)
         if a.denoise:
-            denoised = denoise(r, setup, a.out)
+            denoised = denoise(r, setup, a.out, a.albedo)
     finally:
         r.close()
     print(f"{a.out}: {a.width}x{a.height} @ {a.spp} spp in {dt:.3f} s")
     if a.denoise:
-        print(f"{denoised}: filtered")
+        print(f"{denoised[0]}: filtered")
+        if a.albedo:
+            print(f"{denoised[1]}: filtered on albedo-demodulated radiance")
 
 
-def denoise(r, setup, out):
-    """The finished frame of Renderer `r` through srt_amd.denoise.Denoiser, written beside `out`."""
+def denoise(r, setup, out, albedo=False):
+    """The finished frame of Renderer `r` through srt_amd.denoise.Denoiser, written beside `out`; with `albedo` also
+    through run_albedo on the attrs of srt_amd.surface.Surface.  Returns the paths written."""
     import srt_amd as S
     from srt_amd.denoise import Denoiser
     from srt_amd.query import Query
+    from srt_amd.surface import Surface
 
     out = pathlib.Path(out)
     path = out.with_name(out.stem + "_denoised" + out.suffix)
@@ -105,14 +114,24 @@ def denoise(r, setup, out):
         if setup.scene is not None:
             with Query(setup.scene) as q:
                 q.set_bvh_count(setup.bvh_count)
-                hits = q.closest(dn.primary_rays(setup.camera))
+                rays = dn.primary_rays(setup.camera)
+                hits = q.closest(rays)
                 q.synchronize()
+            if albedo:
+                with Surface(setup.scene) as surf:
+                    surf.set_bvh_count(setup.bvh_count)
+                    attrs = surf.shade(rays, hits)
+                    surf.synchronize()
+                apath = out.with_name(out.stem + "_albedo_denoised" + out.suffix)
+                _, rgba8 = dn.run_albedo(acc_ptr, r.accum_frames, hits, attrs, srgb=True)
+                dn.synchronize()
+                S.write_image(apath, rgba8.cpu().numpy())
         else:
             dn.set_params(passes=0)  # a sphere scene has no mesh to query: the frame passes through
         _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
         dn.synchronize()
         S.write_image(path, rgba8.cpu().numpy())
-    return path
+    return (path, apath) if albedo else (path,)
 
 
 ORBIT_STEP = (0.5, -1.0)  # per frame: MoveRight(0.5), then Rotate(-1 degree of yaw, 0): the camera circles the model
