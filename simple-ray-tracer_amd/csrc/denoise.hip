@@ -12,27 +12,19 @@
 #include "../../include/srt_surface.h"
 #include "denoise.hpp"
 #include "denoise_host.hpp"
+#include "stage.hpp"
 #include "surface_host.hpp"
 
-#define DHIP_OK(expr)                                                         \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
-      return SRT_ERR_HIP;                                                     \
-    }                                                                         \
-  } while (0)
+using srt::stage::Aligned;
+using srt::stage::DevPtr;
 
-struct srt_denoiser {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct srt_denoiser : srt::stage::Stage {
   int width = 0, height = 0;
   srt::denoise::Sizes sizes;
-  float4* d_color[2] = {nullptr, nullptr};  // ping-pong colour | id
-  float4* d_guide = nullptr;                // normal | t
+  DevPtr<float4> d_color[2];  // ping-pong colour | id
+  DevPtr<float4> d_guide;     // normal | t
   srt_denoise_params params;
-  float* d_var[2] = {nullptr, nullptr};     // ping-pong variance (include/srt_variance.h); srt_denoise_enable_variance
+  DevPtr<float> d_var[2];     // ping-pong variance (include/srt_variance.h); srt_denoise_enable_variance
   srt_denoise_var_params var_params;
   int tile_max_step = 0;
   int last_launches = 0;
@@ -45,33 +37,18 @@ using srt::denoise::DParams;
 using srt::denoise::kBlock;
 using srt::denoise::Pass;
 
-void FreeAll(srt_denoiser* dn) {
-  for (float4* p : dn->d_color)
-    if (p) (void)hipFree(p);
-  if (dn->d_guide) (void)hipFree(dn->d_guide);
-  for (float* p : dn->d_var)
-    if (p) (void)hipFree(p);
-  if (dn->own_stream && dn->stream) (void)hipStreamDestroy(dn->stream);
-}
-
 int Allocate(srt_denoiser* dn) {
-  DHIP_OK(hipSetDevice(dn->device));
-  if (!dn->stream) {
-    DHIP_OK(hipStreamCreateWithFlags(&dn->stream, hipStreamNonBlocking));
-    dn->own_stream = true;
-  }
-  DHIP_OK(hipMalloc(&dn->d_color[0], dn->sizes.color_bytes));
-  DHIP_OK(hipMalloc(&dn->d_color[1], dn->sizes.color_bytes));
-  DHIP_OK(hipMalloc(&dn->d_guide, dn->sizes.guide_bytes));
+  STAGE_HIP_OK(srt::stage::AllocPair(dn->d_color, dn->sizes.color_bytes));
+  STAGE_HIP_OK(dn->d_guide.Alloc(dn->sizes.guide_bytes));
   const size_t lds = dn->tile_max_step ? srt::denoise::TileLdsBytes(dn->tile_max_step) : 0;
   if (lds > 48 * 1024) {
-    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true>,
+    STAGE_HIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false>,
+    STAGE_HIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true, AParams>,
+    STAGE_HIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<true, AParams>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DHIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false, AParams>,
+    STAGE_HIP_OK(hipFuncSetAttribute((const void*)srt::denoise::denoise_tiled_kernel<false, AParams>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   return SRT_OK;
@@ -103,12 +80,12 @@ int Run(srt_denoiser* dn, const char* what, const void* accum_rgba32f_dev, int f
     srt::SetError(std::string(what) + ": a guide is needed when passes > 0");
     return SRT_ERR_INVALID;
   }
-  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u) ||
-      ((uintptr_t)out_rgba8_dev & 3u)) {
+  if (!Aligned(accum_rgba32f_dev, 16) || !Aligned(guide_dev, 16) || !Aligned(out_rgba32f_dev, 16) ||
+      !Aligned(out_rgba8_dev, 4)) {
     srt::SetError(std::string(what) + ": accum, guide and out_rgba32f must be 16-byte aligned, out_rgba8 4-byte");
     return SRT_ERR_INVALID;
   }
-  DHIP_OK(hipSetDevice(dn->device));
+  STAGE_HIP_OK(hipSetDevice(dn->device));
   AParams dp;
   std::memset(&dp, 0, sizeof dp);
   dp.hits = reinterpret_cast<const uint4*>(guide_dev);
@@ -131,7 +108,7 @@ int Run(srt_denoiser* dn, const char* what, const void* accum_rgba32f_dev, int f
     const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(srt::denoise::denoise_resolve_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream,
                        static_cast<const DParams&>(dp));
-    DHIP_OK(hipGetLastError());
+    STAGE_HIP_OK(hipGetLastError());
     dn->last_launches = 1;
     return SRT_OK;
   }
@@ -147,7 +124,7 @@ int Run(srt_denoiser* dn, const char* what, const void* accum_rgba32f_dev, int f
       LaunchPass<AParams>(dn, ps, dp);
     else
       LaunchPass<DParams>(dn, ps, dp);
-    DHIP_OK(hipGetLastError());
+    STAGE_HIP_OK(hipGetLastError());
   }
   dn->last_launches = n;
   return SRT_OK;
@@ -168,34 +145,26 @@ int srt_denoise_create(int device, void* stream, int width, int height, srt_deno
                                       : "srt_denoise_create: width and height must be at least 1");
     return rc;
   }
-  srt_denoiser* dn = new srt_denoiser();
-  dn->device = device;
-  dn->stream = static_cast<hipStream_t>(stream);
+  srt::stage::Owned<srt_denoiser> dn(new srt_denoiser());
   dn->width = width;
   dn->height = height;
   dn->sizes = sizes;
   dn->params = srt::denoise::DefaultParams();
   dn->var_params = srt::denoise::DefaultVarParams();
   dn->tile_max_step = srt::denoise::TileMaxStep(std::getenv("SRT_DENOISE_TILE"));
-  if (int rc = Allocate(dn)) {
-    FreeAll(dn);
-    delete dn;
-    return rc;
-  }
-  *out = dn;
+  if (int rc = dn->Acquire(device, stream)) return rc;
+  if (int rc = Allocate(dn.get())) return rc;
+  *out = dn.release();
   return SRT_OK;
 }
 
 int srt_denoise_destroy(srt_denoiser* dn) {
   if (!dn) return SRT_ERR_INVALID;
-  (void)hipSetDevice(dn->device);
-  if (dn->stream) (void)hipStreamSynchronize(dn->stream);
-  FreeAll(dn);
-  delete dn;
+  srt::stage::Destroy()(dn);
   return SRT_OK;
 }
 
-void* srt_denoise_stream(srt_denoiser* dn) { return dn ? dn->stream : nullptr; }
+void* srt_denoise_stream(srt_denoiser* dn) { return srt::stage::StreamOf(dn); }
 
 int srt_denoise_get_int(srt_denoiser* dn, const char* name, int* v) {
   if (!dn || !name || !v) return SRT_ERR_INVALID;
@@ -204,16 +173,13 @@ int srt_denoise_get_int(srt_denoiser* dn, const char* name, int* v) {
   else if (n == "normal_squarings") *v = (int)dn->params.normal_squarings;
   else if (n == "width") *v = dn->width;
   else if (n == "height") *v = dn->height;
-  else if (n == "scratch.bytes") *v = (int)(dn->sizes.scratch_bytes < 0x7FFFFFFFu ? dn->sizes.scratch_bytes : 0x7FFFFFFFu);
+  else if (n == "scratch.bytes") *v = srt::stage::SaturateInt(dn->sizes.scratch_bytes);
   else if (n == "tile.lds_bytes") *v = dn->tile_max_step ? (int)srt::denoise::TileLdsBytes(dn->tile_max_step) : 0;
   else if (n == "tile.max_step") *v = dn->tile_max_step;
   else if (n == "tile.width") *v = srt::denoise::kTileW;
   else if (n == "tile.height") *v = srt::denoise::kTileH;
   else if (n == "launches") *v = dn->last_launches;
-  else if (n == "variance.bytes") {
-    const size_t b = dn->d_var[0] ? 2 * srt::denoise::VarianceBytes(dn->sizes) : 0;
-    *v = (int)(b < 0x7FFFFFFFu ? b : 0x7FFFFFFFu);
-  }
+  else if (n == "variance.bytes") *v = srt::stage::SaturateInt(dn->d_var[0] ? 2 * srt::denoise::VarianceBytes(dn->sizes) : 0);
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -236,7 +202,7 @@ int srt_denoise_set_params(srt_denoiser* dn, const srt_denoise_params* p) {
 
 int srt_denoise_primary_rays(srt_denoiser* dn, const float origin[3], const float front[3], const float right[3],
                              const float up[3], srt_ray* rays_dev) {
-  if (!dn || !origin || !front || !right || !up || !rays_dev || ((uintptr_t)rays_dev & 15u)) return SRT_ERR_INVALID;
+  if (!dn || !origin || !front || !right || !up || !rays_dev || !Aligned(rays_dev, 16)) return SRT_ERR_INVALID;
   srt::denoise::Basis b;
   srt::denoise::PrimaryBasis(origin, front, right, up, dn->width, dn->height, &b);
   srt::denoise::RayParams rp;
@@ -247,10 +213,10 @@ int srt_denoise_primary_rays(srt_denoiser* dn, const float origin[3], const floa
   std::memcpy(rp.p00, b.p00, sizeof rp.p00);
   std::memcpy(rp.du, b.du, sizeof rp.du);
   std::memcpy(rp.dv, b.dv, sizeof rp.dv);
-  DHIP_OK(hipSetDevice(dn->device));
+  STAGE_HIP_OK(hipSetDevice(dn->device));
   const unsigned blocks = (unsigned)((dn->sizes.pixels + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(srt::denoise::primary_rays_kernel, dim3(blocks), dim3(kBlock), 0, dn->stream, rp);
-  DHIP_OK(hipGetLastError());
+  STAGE_HIP_OK(hipGetLastError());
   return SRT_OK;
 }
 
@@ -268,7 +234,7 @@ int srt_denoise_run_albedo(srt_denoiser* dn, const void* accum_rgba32f_dev, int 
   }
   if (!dn) return SRT_ERR_INVALID;
   if (dn->params.passes == 0) attrs_dev = nullptr;  // ignored: srt_denoise_run's result
-  else if (!attrs_dev || ((uintptr_t)attrs_dev & 15u)) {
+  else if (!attrs_dev || !Aligned(attrs_dev, 16)) {
     srt::SetError("srt_denoise_run_albedo: attrs are needed when passes > 0, 16-byte aligned");
     return SRT_ERR_INVALID;
   }
@@ -281,18 +247,8 @@ int srt_variance_abi_version(void) { return SRT_VARIANCE_ABI_VERSION; }
 int srt_denoise_enable_variance(srt_denoiser* dn) {
   if (!dn) return SRT_ERR_INVALID;
   if (dn->d_var[0]) return SRT_OK;
-  DHIP_OK(hipSetDevice(dn->device));
-  float* v[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2; ++k) {
-    const hipError_t e = hipMalloc(&v[k], srt::denoise::VarianceBytes(dn->sizes));
-    if (e != hipSuccess) {
-      if (v[0]) (void)hipFree(v[0]);
-      srt::SetError(std::string("srt_denoise_enable_variance: hipMalloc: ") + hipGetErrorString(e));
-      return SRT_ERR_HIP;
-    }
-  }
-  dn->d_var[0] = v[0];
-  dn->d_var[1] = v[1];
+  STAGE_HIP_OK(hipSetDevice(dn->device));
+  STAGE_HIP_OK(srt::stage::AllocPair(dn->d_var, srt::denoise::VarianceBytes(dn->sizes)));
   return SRT_OK;
 }
 
@@ -323,8 +279,8 @@ int srt_denoise_run_variance(srt_denoiser* dn, const void* colour_rgba32f_dev, i
     srt::SetError("srt_denoise_run_variance: call srt_denoise_enable_variance first");
     return SRT_ERR_INVALID;
   }
-  if (((uintptr_t)colour_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)moments_dev & 15u) ||
-      ((uintptr_t)out_rgba32f_dev & 15u) || ((uintptr_t)out_rgba8_dev & 3u) || ((uintptr_t)out_var_f32_dev & 3u)) {
+  if (!Aligned(colour_rgba32f_dev, 16) || !Aligned(guide_dev, 16) || !Aligned(moments_dev, 16) ||
+      !Aligned(out_rgba32f_dev, 16) || !Aligned(out_rgba8_dev, 4) || !Aligned(out_var_f32_dev, 4)) {
     srt::SetError("srt_denoise_run_variance: colour, guide, moments and out_rgba32f must be 16-byte aligned, out_rgba8 and out_var 4-byte");
     return SRT_ERR_INVALID;
   }
@@ -334,7 +290,7 @@ int srt_denoise_run_variance(srt_denoiser* dn, const void* colour_rgba32f_dev, i
     srt::SetError("srt_denoise_run_variance: passes must be at least 1");
     return SRT_ERR_INVALID;
   }
-  DHIP_OK(hipSetDevice(dn->device));
+  STAGE_HIP_OK(hipSetDevice(dn->device));
   srt::denoise::VParams vp;
   std::memset(&vp, 0, sizeof vp);
   vp.hits = reinterpret_cast<const uint4*>(guide_dev);
@@ -362,7 +318,7 @@ int srt_denoise_run_variance(srt_denoiser* dn, const void* colour_rgba32f_dev, i
       hipLaunchKernelGGL(srt::denoise::variance_resolve_kernel, grid, dim3(kBlock), 0, dn->stream, vp);
     else
       hipLaunchKernelGGL(srt::denoise::variance_pass_kernel, grid, dim3(kBlock), 0, dn->stream, vp);
-    DHIP_OK(hipGetLastError());
+    STAGE_HIP_OK(hipGetLastError());
   }
   dn->last_launches = n;
   return SRT_OK;

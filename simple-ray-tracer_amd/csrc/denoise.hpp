@@ -11,18 +11,18 @@
 //                          float4 = every bank once per ds_read_b128 lane group, whatever the row stride)
 //   denoise_direct_kernel  large steps, where the halo outgrows the tile: taps are global dwordx4 loads, a
 //                          wave covering 64 contiguous pixels of one row
-// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division); the
-// sRGB8 encode is device_common.hpp's linearToSrgb / to_unorm8, read-only, as accumulate_kernel uses them.
+// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division).  The 16-B
+// loads, the hit unpacking, the normal and depth weights, the luminance and the sRGB8 encode are image_device.hpp's,
+// shared with temporal.hpp.
 #pragma once
 
-#include "device_common.hpp"
 #include "denoise_host.hpp"
+#include "image_device.hpp"
 
 namespace srt {
 namespace denoise {
 using namespace dev;
-
-constexpr uint32_t kMissId = 0xFFFFFFFFu;
+using namespace image;
 
 struct DParams {
   const float4* src;   // colour | id of the previous pass; first pass: the accumulation image (sum | 1)
@@ -62,23 +62,7 @@ __device__ __forceinline__ f3 albedo_of(const AParams& ap, int p) {
 }
 
 __device__ __forceinline__ uint32_t px_id(const float4& c) { return __float_as_uint(c.w); }
-__device__ __forceinline__ bool finite1(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ bool finite3(const float4& c) { return finite1(c.x) && finite1(c.y) && finite1(c.z); }
-
-// A whole 16-B word in one instruction (dwordx4 / ds_read_b128): the empty asm makes all four components
-// live, or the compiler splits the load at the component the id test reads first.
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld16(const float4* p) {
-  v4f v = *reinterpret_cast<const v4f*>(p);
-  asm("" : "+v"(v));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint4 ld16(const uint4* p) {
-  v4u v = *reinterpret_cast<const v4u*>(p);
-  asm("" : "+v"(v));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 
 template <bool FIRST, class P = DParams>
 __device__ __forceinline__ Px load_px(const P& dp, int p) {
@@ -93,8 +77,8 @@ __device__ __forceinline__ Px load_px(const P& dp, int p) {
         o = mk(o.x / al.x, o.y / al.y, o.z / al.z);
       }
     }
-    r.c = make_float4(o.x, o.y, o.z, __uint_as_float(h0.x == kMissId ? kMissId : h1.z));
-    r.g = make_float4(__uint_as_float(h0.z), __uint_as_float(h0.w), __uint_as_float(h1.x), __uint_as_float(h0.y));
+    r.c = make_float4(o.x, o.y, o.z, __uint_as_float(hit_id(h0, h1)));
+    r.g = hit_guide(h0, h1);
   } else {
     r.c = ld16(dp.src + p);
     r.g = ld16(dp.guide + p);
@@ -106,11 +90,10 @@ __device__ __forceinline__ Px load_px(const P& dp, int p) {
 __device__ __forceinline__ void tap(const DParams& dp, const Px& p, bool pfin, const float4& cq, const float4& gq, float k,
                                     float& sw, f3& sum) {
   if (px_id(cq) != px_id(p.c) || !finite3(cq)) return;  // a miss, outside the image, another BVH record, or not finite
-  const float dot = p.g.x * gq.x + p.g.y * gq.y + p.g.z * gq.z;
+  const float dot = p.g.x * gq.x + p.g.y * gq.y + p.g.z * gq.z;  // not weight_n: inlined here it inverts a branch of the pass kernels
   float wn = dot > 0.0f ? dot : 0.0f;
   for (int i = 0; i < dp.nsq; ++i) wn = wn * wn;
-  const float xz = __builtin_fabsf(p.g.w - gq.w) / (dp.sigma_d * (p.g.w + gq.w));
-  const float wz = 1.0f / ((1.0f + xz) * (1.0f + xz));
+  const float wz = weight_z(p.g, gq, dp.sigma_d);
   float wc = 1.0f;
   if (pfin) {
     const float dx = p.c.x - cq.x, dy = p.c.y - cq.y, dz = p.c.z - cq.z;
@@ -139,10 +122,7 @@ __device__ __forceinline__ void store_px(const P& dp, int i, const Px& p, f3 c) 
     if (!dp.dst && px_id(p.c) != kMissId) c = c * albedo_of(dp, i);  // the last pass: radiance again
   }
   if (dp.out32) dp.out32[i] = make_float4(c.x, c.y, c.z, 1.0f);
-  if (dp.out8) {
-    const uint32_t r = to_unorm8(linearToSrgb(c.x)), g = to_unorm8(linearToSrgb(c.y)), b = to_unorm8(linearToSrgb(c.z));
-    dp.out8[i] = r | (g << 8) | (b << 16) | (255u << 24);
-  }
+  if (dp.out8) dp.out8[i] = pack_srgb8(c);
 }
 
 template <bool FIRST, class P = DParams>
@@ -253,19 +233,6 @@ struct VParams {
   float min_history;      // resolve: float(min_history)
 };
 
-__device__ __forceinline__ float lum3(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
-__device__ __forceinline__ float weight_n(const VParams& vp, const float4& gp, const float4& gq) {
-  const float dot = gp.x * gq.x + gp.y * gq.y + gp.z * gq.z;
-  float wn = dot > 0.0f ? dot : 0.0f;
-  for (int i = 0; i < vp.nsq; ++i) wn = wn * wn;
-  return wn;
-}
-__device__ __forceinline__ float weight_z(const VParams& vp, const float4& gp, const float4& gq) {
-  const float xz = __builtin_fabsf(gp.w - gq.w) / (vp.sigma_d * (gp.w + gq.w));
-  return 1.0f / ((1.0f + xz) * (1.0f + xz));
-}
-
 __global__ __launch_bounds__(kBlock) void variance_resolve_kernel(VParams vp) {
   const int x = (int)blockIdx.x * kDirectW + ((int)threadIdx.x & (kDirectW - 1));
   const int y = (int)blockIdx.y * kDirectH + (int)threadIdx.x / kDirectW;
@@ -275,8 +242,8 @@ __global__ __launch_bounds__(kBlock) void variance_resolve_kernel(VParams vp) {
   const uint4 h0 = ld16(vp.hits + 2 * (size_t)pi), h1 = ld16(vp.hits + 2 * (size_t)pi + 1);
   const float4 m = ld16(vp.moments + pi);
   const f3 o = mk(a.x, a.y, a.z) / vp.frames;
-  const uint32_t id = h0.x == kMissId ? kMissId : h1.z;
-  const float4 gp = make_float4(__uint_as_float(h0.z), __uint_as_float(h0.w), __uint_as_float(h1.x), __uint_as_float(h0.y));
+  const uint32_t id = hit_id(h0, h1);
+  const float4 gp = hit_guide(h0, h1);
   float var = 0.0f;
   if (id != kMissId) {
     if (m.w >= vp.min_history) {
@@ -291,9 +258,9 @@ __global__ __launch_bounds__(kBlock) void variance_resolve_kernel(VParams vp) {
           const int qi = qy * vp.W + qx;
           const uint4 q0 = ld16(vp.hits + 2 * (size_t)qi), q1 = ld16(vp.hits + 2 * (size_t)qi + 1);
           const float4 mq = ld16(vp.moments + qi);
-          if ((q0.x == kMissId ? kMissId : q1.z) != id || !finite1(mq.x) || !finite1(mq.y)) continue;
-          const float4 gq = make_float4(__uint_as_float(q0.z), __uint_as_float(q0.w), __uint_as_float(q1.x), __uint_as_float(q0.y));
-          const float w = weight_n(vp, gp, gq) * weight_z(vp, gp, gq);
+          if (hit_id(q0, q1) != id || !finite1(mq.x) || !finite1(mq.y)) continue;
+          const float4 gq = hit_guide(q0, q1);
+          const float w = weight_n(gp, gq, vp.nsq) * weight_z(gp, gq, vp.sigma_d);
           s1 += w * mq.x;
           s2 += w * mq.y;
           sw += w;
@@ -343,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void variance_pass_kernel(VParams vp) {
     }
     const float g = sk > 0.0f ? sg / sk : 0.0f;
     const float sl = vp.sigma_l * __builtin_sqrtf(g) + 1e-4f;
-    const float Lp = lum3(p.c.x, p.c.y, p.c.z);
+    const float Lp = lum(p.c.x, p.c.y, p.c.z);
     const bool lfin = finite1(Lp);
     float sw = 0.0f, sv = 0.0f;
     f3 sum = mk(0.0f, 0.0f, 0.0f);
@@ -361,10 +328,10 @@ __global__ __launch_bounds__(kBlock) void variance_pass_kernel(VParams vp) {
         if (px_id(cq) != px_id(p.c) || !finite3(cq)) continue;
         float wl = 1.0f;
         if (lfin) {
-          const float xl = __builtin_fabsf(Lp - lum3(cq.x, cq.y, cq.z)) / sl;
+          const float xl = __builtin_fabsf(Lp - lum(cq.x, cq.y, cq.z)) / sl;
           wl = 1.0f / ((1.0f + xl) * (1.0f + xl));
         }
-        const float w = (((tap_h(dx) * tap_h(dy)) * weight_n(vp, p.g, gq)) * weight_z(vp, p.g, gq)) * wl;
+        const float w = (((tap_h(dx) * tap_h(dy)) * weight_n(p.g, gq, vp.nsq)) * weight_z(p.g, gq, vp.sigma_d)) * wl;
         if (!(w > 0.0f)) continue;
         sw += w;
         sum.x += w * cq.x;
@@ -381,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void variance_pass_kernel(VParams vp) {
   if (vp.dst) vp.dst[pi] = make_float4(c.x, c.y, c.z, p.c.w);
   if (vp.vdst) vp.vdst[pi] = var;
   if (vp.out32) vp.out32[pi] = make_float4(c.x, c.y, c.z, 1.0f);
-  if (vp.out8) {
+  if (vp.out8) {  // not pack_srgb8: inlined here it swaps two operands of the kernel's v_or3_b32
     const uint32_t r = to_unorm8(linearToSrgb(c.x)), g = to_unorm8(linearToSrgb(c.y)), b = to_unorm8(linearToSrgb(c.z));
     vp.out8[pi] = r | (g << 8) | (b << 16) | (255u << 24);
   }
@@ -399,9 +366,9 @@ __global__ __launch_bounds__(kBlock) void primary_rays_kernel(RayParams rp) {
   if (p >= rp.W * rp.H) return;
   const int j = p / rp.W, i = p - j * rp.W;
   const float fi = (float)i, fj = (float)j;
-  const float dx = ((rp.p00[0] + fi * rp.du[0]) + fj * rp.dv[0]) - rp.o[0];
-  const float dy = ((rp.p00[1] + fi * rp.du[1]) + fj * rp.dv[1]) - rp.o[1];
-  const float dz = ((rp.p00[2] + fi * rp.du[2]) + fj * rp.dv[2]) - rp.o[2];
+  const float dx = pixel_dir(rp.p00[0], rp.du[0], rp.dv[0], rp.o[0], fi, fj);
+  const float dy = pixel_dir(rp.p00[1], rp.du[1], rp.dv[1], rp.o[1], fi, fj);
+  const float dz = pixel_dir(rp.p00[2], rp.du[2], rp.dv[2], rp.o[2], fi, fj);
   rp.rays[2 * (size_t)p] = make_float4(rp.o[0], rp.o[1], rp.o[2], 0.0f);
   rp.rays[2 * (size_t)p + 1] = make_float4(dx, dy, dz, 1e30f);
 }

@@ -12,26 +12,16 @@
 #include "../../include/srt_query.h"
 #include "query.hpp"
 #include "query_host.hpp"
+#include "stage.hpp"
 
-#define QHIP_OK(expr)                                                         \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
-      return SRT_ERR_HIP;                                                     \
-    }                                                                         \
-  } while (0)
+using srt::stage::Aligned;
+using srt::stage::DevPtr;
 
-struct srt_query {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  float4* d_pairs = nullptr;
-  float4* d_roots = nullptr;
-  float4* d_tris = nullptr;
-  float* d_frames = nullptr;
-  uint32_t* d_ctr = nullptr;
-  uint32_t* d_stack = nullptr;  // HBM stacks of `stack_blocks` blocks (deep trees only)
+struct srt_query : srt::stage::Stage {
+  DevPtr<float4> d_pairs, d_roots, d_tris;
+  DevPtr<float> d_frames;
+  DevPtr<uint32_t> d_ctr;
+  DevPtr<uint32_t> d_stack;  // HBM stacks of `stack_blocks` blocks (deep trees only)
   int stack_blocks = 0;
   size_t scene_bytes = 0;
   uint32_t n_bvhs = 0, bvh_count = 0;
@@ -61,46 +51,31 @@ const void* Instance(bool hbm, bool pack) {
               : (const void*)srt::query::query_kernel<ANY, false, false>;
 }
 
-void FreeAll(srt_query* q) {
-  if (q->d_pairs) (void)hipFree(q->d_pairs);
-  if (q->d_roots) (void)hipFree(q->d_roots);
-  if (q->d_tris) (void)hipFree(q->d_tris);
-  if (q->d_frames) (void)hipFree(q->d_frames);
-  if (q->d_ctr) (void)hipFree(q->d_ctr);
-  if (q->d_stack) (void)hipFree(q->d_stack);
-  if (q->own_stream && q->stream) (void)hipStreamDestroy(q->stream);
-}
-
 int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bvhs) {
-  QHIP_OK(hipSetDevice(q->device));
-  if (!q->stream) {
-    QHIP_OK(hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking));
-    q->own_stream = true;
-  }
   std::vector<float> frames(16 * ((size_t)q->n_bvhs + 1), 0.0f);
   for (uint32_t b = 0; b < q->n_bvhs; ++b) std::memcpy(&frames[16 * (size_t)b], bvhs[b].frame, 16 * sizeof(float));
   const size_t pb = lay.pairs.size() * sizeof(float4), rb = lay.roots.size() * sizeof(float4),
                tb = lay.tris.size() * sizeof(float4), fb = frames.size() * sizeof(float);
-  QHIP_OK(hipMalloc(&q->d_pairs, pb));
-  QHIP_OK(hipMalloc(&q->d_roots, rb));
-  QHIP_OK(hipMalloc(&q->d_tris, tb));
-  QHIP_OK(hipMalloc(&q->d_frames, fb));
-  QHIP_OK(hipMalloc(&q->d_ctr, 256));
-  QHIP_OK(hipMemcpyAsync(q->d_pairs, lay.pairs.data(), pb, hipMemcpyHostToDevice, q->stream));
-  QHIP_OK(hipMemcpyAsync(q->d_roots, lay.roots.data(), rb, hipMemcpyHostToDevice, q->stream));
-  QHIP_OK(hipMemcpyAsync(q->d_tris, lay.tris.data(), tb, hipMemcpyHostToDevice, q->stream));
-  QHIP_OK(hipMemcpyAsync(q->d_frames, frames.data(), fb, hipMemcpyHostToDevice, q->stream));
-  QHIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
+  STAGE_HIP_OK(q->d_pairs.Alloc(pb));
+  STAGE_HIP_OK(q->d_roots.Alloc(rb));
+  STAGE_HIP_OK(q->d_tris.Alloc(tb));
+  STAGE_HIP_OK(q->d_frames.Alloc(fb));
+  STAGE_HIP_OK(q->d_ctr.Alloc(256));
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_pairs, lay.pairs.data(), pb, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_roots, lay.roots.data(), rb, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_tris, lay.tris.data(), tb, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_frames, frames.data(), fb, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
   q->scene_bytes = pb + rb + tb + fb;
   // persistent grid: the blocks the device holds at once
   hipDeviceProp_t prop;
-  QHIP_OK(hipGetDeviceProperties(&prop, q->device));
+  STAGE_HIP_OK(hipGetDeviceProperties(&prop, q->device));
   for (int any = 0; any < 2; ++any) {
     const void* fn = any ? Instance<true>(q->plan.in_hbm, q->plan.packed) : Instance<false>(q->plan.in_hbm, q->plan.packed);
     if (q->plan.lds_bytes > 48 * 1024)
-      QHIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
+      STAGE_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
     int per_cu = 0;
-    QHIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
+    STAGE_HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
     per_cu = std::max(1, std::min(per_cu, LdsBlocksPerCu(q->plan.lds_bytes)));
     if (q->plan.in_hbm) per_cu = std::min(per_cu, 4);  // each block holds an HBM stack area
     q->max_blocks[any] = per_cu * std::max(1, prop.multiProcessorCount);
@@ -112,7 +87,7 @@ template <bool ANY>
 int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
   if (!q || (n && (!rays || !out))) return SRT_ERR_INVALID;
   if (n == 0) return SRT_OK;
-  if (((uintptr_t)rays & 15u) || (!ANY && ((uintptr_t)out & 15u))) {
+  if (!Aligned(rays, 16) || (!ANY && !Aligned(out, 16))) {
     srt::SetError("srt_query: rays and hits must be 16-byte aligned");
     return SRT_ERR_INVALID;
   }
@@ -120,13 +95,12 @@ int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
     srt::SetError("srt_query: more than 2^32 - 2^20 rays in one call");
     return SRT_ERR_LIMIT;
   }
-  QHIP_OK(hipSetDevice(q->device));
+  STAGE_HIP_OK(hipSetDevice(q->device));
   const int blocks = (int)std::min<uint64_t>((uint64_t)q->max_blocks[ANY ? 1 : 0], ((uint64_t)n + kBlock - 1) / kBlock);
   if (q->plan.in_hbm && blocks > q->stack_blocks) {  // grown when n grows (hipFree waits for the device)
-    if (q->d_stack) (void)hipFree(q->d_stack);
-    q->d_stack = nullptr;
+    q->d_stack.Free();
     q->stack_blocks = 0;
-    QHIP_OK(hipMalloc(&q->d_stack, q->plan.hbm_block_bytes * (size_t)blocks));
+    STAGE_HIP_OK(q->d_stack.Alloc(q->plan.hbm_block_bytes * (size_t)blocks));
     q->stack_blocks = blocks;
   }
   QParams qp;
@@ -148,9 +122,9 @@ int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
   qp.claim = 64u * (uint32_t)(q->claim_env > 0 ? q->claim_env : std::max<uint64_t>(1, std::min<uint64_t>(4, per)));
   qp.stack_entries = q->plan.entries;
   qp.refill_min = q->refill_min;
-  QHIP_OK(hipMemsetAsync(q->d_ctr, 0, sizeof(uint32_t), q->stream));
+  STAGE_HIP_OK(hipMemsetAsync(q->d_ctr, 0, sizeof(uint32_t), q->stream));
   void* args[] = {&qp};
-  QHIP_OK(hipLaunchKernel(Instance<ANY>(q->plan.in_hbm, q->plan.packed), dim3((unsigned)blocks), dim3(kBlock), args,
+  STAGE_HIP_OK(hipLaunchKernel(Instance<ANY>(q->plan.in_hbm, q->plan.packed), dim3((unsigned)blocks), dim3(kBlock), args,
                           q->plan.lds_bytes, q->stream));
   q->last_blocks = blocks;
   return SRT_OK;
@@ -178,9 +152,7 @@ int srt_query_create(int device, void* stream, const srt_bvh_record* bvhs, uint3
     srt::SetError("BVH deeper than the query traversal stack supports (2^20 levels)");
     return SRT_ERR_LIMIT;
   }
-  srt_query* q = new srt_query();
-  q->device = device;
-  q->stream = static_cast<hipStream_t>(stream);
+  srt::stage::Owned<srt_query> q(new srt_query());
   q->n_bvhs = q->bvh_count = n_bvhs;
   q->plan = srt::query::PlanStack(lay, n_tris);
   // Refill threshold ("Ray queries"): a scene the caches hold (Rubik, 74 KB) gains from
@@ -192,37 +164,23 @@ int srt_query_create(int device, void* stream, const srt_bvh_record* bvhs, uint3
   q->refill_min = std::max(1, std::min(64, e ? std::atoi(e) : (scene_bytes < (1u << 20) ? 48 : 1)));
   e = std::getenv("SRT_QUERY_CLAIM");
   q->claim_env = e ? std::max(0, std::min(64, std::atoi(e))) : 0;
-  if (int rc = Upload(q, lay, bvhs)) {
-    FreeAll(q);
-    delete q;
-    return rc;
-  }
-  *out = q;
+  if (int rc = q->Acquire(device, stream)) return rc;
+  if (int rc = Upload(q.get(), lay, bvhs)) return rc;
+  *out = q.release();
   return SRT_OK;
 }
 
 int srt_query_create_obj(int device, void* stream, const srt_scene* s, srt_query** out) {
   if (!s || !out) return SRT_ERR_INVALID;
-  uint32_t sz[5] = {0, 0, 0, 0, 0};
-  if (int rc = srt_scene_sizes(s, sz)) return rc;
-  std::vector<srt_bvh_record> bvhs(sz[0]);
-  std::vector<srt_bvh_node> nodes(sz[1]);
-  std::vector<srt_material_obj> mats(sz[2]);
-  std::vector<float> alb(3 * (size_t)sz[2]);
-  std::vector<srt_triangle> tris(sz[3]);
-  std::vector<srt_vertex> verts(sz[4]);
-  if (int rc = srt_scene_copy(s, bvhs.data(), nodes.data(), mats.data(), alb.data(), tris.data(), verts.data()))
-    return rc;
-  return srt_query_create(device, stream, bvhs.data(), sz[0], nodes.data(), sz[1], tris.data(), sz[3], verts.data(),
-                          sz[4], out);
+  srt::stage::SceneArrays a;
+  if (int rc = srt::stage::CopyScene(s, &a)) return rc;
+  return srt_query_create(device, stream, a.bvhs.data(), (uint32_t)a.bvhs.size(), a.nodes.data(), (uint32_t)a.nodes.size(),
+                          a.tris.data(), (uint32_t)a.tris.size(), a.verts.data(), (uint32_t)a.verts.size(), out);
 }
 
 int srt_query_destroy(srt_query* q) {
   if (!q) return SRT_ERR_INVALID;
-  (void)hipSetDevice(q->device);
-  if (q->stream) (void)hipStreamSynchronize(q->stream);
-  FreeAll(q);
-  delete q;
+  srt::stage::Destroy()(q);
   return SRT_OK;
 }
 
@@ -238,9 +196,9 @@ int srt_query_update_model_matrix(srt_query* q, uint32_t index, const float fram
     srt::SetError("UpdateModelMatrix: index out of range");
     return SRT_ERR_INVALID;
   }
-  QHIP_OK(hipSetDevice(q->device));
+  STAGE_HIP_OK(hipSetDevice(q->device));
   // ordered with the queries on the stream; the 64 B leave `frame` before the call returns
-  QHIP_OK(hipMemcpyAsync(q->d_frames + 16 * (size_t)index, frame, 16 * sizeof(float), hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_frames + 16 * (size_t)index, frame, 16 * sizeof(float), hipMemcpyHostToDevice, q->stream));
   return SRT_OK;
 }
 
@@ -260,14 +218,14 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   else if (n == "stack.packed") *v = q->plan.packed ? 1 : 0;
   else if (n == "launch.blocks") *v = q->last_blocks;
   else if (n == "launch.block") *v = kBlock;
-  else if (n == "scratch.bytes") *v = (int)std::min<size_t>(0x7FFFFFFF, 256 + q->plan.hbm_block_bytes * (size_t)q->stack_blocks);
-  else if (n == "scene.bytes") *v = (int)std::min<size_t>(0x7FFFFFFF, q->scene_bytes);
+  else if (n == "scratch.bytes") *v = srt::stage::SaturateInt(256 + q->plan.hbm_block_bytes * (size_t)q->stack_blocks);
+  else if (n == "scene.bytes") *v = srt::stage::SaturateInt(q->scene_bytes);
   else if (n == "refill.min") *v = q->refill_min;
   else if (n == "bvh_count") *v = (int)q->bvh_count;
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
 
-void* srt_query_stream(srt_query* q) { return q ? q->stream : nullptr; }
+void* srt_query_stream(srt_query* q) { return srt::stage::StreamOf(q); }
 
 }  // extern "C"

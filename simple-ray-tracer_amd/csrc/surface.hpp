@@ -10,14 +10,13 @@
 // pt_math.hpp is only read.
 #pragma once
 
-#include "device_common.hpp"
+#include "image_device.hpp"
 #include "surface_host.hpp"
 
 namespace srt {
 namespace surface {
 using namespace dev;
-
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
+using namespace image;
 
 struct SParams {
   const float4* frames;     // 4 float4 (the columns) per BVH record, n_bvhs + 1 records (the last: zeros)
@@ -32,19 +31,7 @@ struct SParams {
   uint32_t n_bvhs, bvh_count, n_tris, n_tex;
 };
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-// A whole 16-B word in one instruction: the empty asm keeps all four components live (denoise.hpp's ld16).
-__device__ __forceinline__ float4 ld16(const float4* p) {
-  v4f v = *reinterpret_cast<const v4f*>(p);
-  asm("" : "+v"(v));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint4 ld16(const uint4* p) {
-  v4u v = *reinterpret_cast<const v4u*>(p);
-  asm("" : "+v"(v));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
+// A whole 16-B word in one store, as image_device.hpp's ld16 loads one.
 __device__ __forceinline__ void st16(float4* p, float x, float y, float z, float w) {
   v4f v = {x, y, z, w};
   *reinterpret_cast<v4f*>(p) = v;
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void surface_shade_kernel(SParams sp) {
   const uint4 h0 = ld16(sp.hits + 2 * (size_t)i), h1 = ld16(sp.hits + 2 * (size_t)i + 1);  // triangle t n.x n.y | n.z material bvh pad
   float4* const o = sp.out + 2 * (size_t)i;
   const uint32_t tri = h0.x;
-  if (tri >= sp.n_tris) {  // a miss (kMiss), or an index no triangle of the scene has
+  if (tri >= sp.n_tris) {  // a miss (kMissId), or an index no triangle of the scene has
     st16(o, 0.0f, 0.0f, 0.0f, 0.0f);
     st16(o + 1, 0.0f, 0.0f, 0.0f, 0.0f);
     return;

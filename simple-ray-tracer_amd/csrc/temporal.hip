@@ -10,62 +10,35 @@
 #include "../../include/srt_temporal_motion.h"
 #include "../../include/srt_variance.h"
 #include "denoise_host.hpp"
-#include "srt_internal.hpp"
+#include "stage.hpp"
 #include "temporal.hpp"
 #include "temporal_host.hpp"
 
-#define THIP_OK(expr)                                                         \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      srt::SetError(std::string(#expr) + ": " + hipGetErrorString(e_));       \
-      return SRT_ERR_HIP;                                                     \
-    }                                                                         \
-  } while (0)
+using srt::stage::Aligned;
+using srt::stage::DevPtr;
 
-struct srt_temporal {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+struct srt_temporal : srt::stage::Stage {
   int width = 0, height = 0;
   srt::temporal::Sizes sizes;
-  float4* d_color[2] = {nullptr, nullptr};  // rgb | N
-  float4* d_guide[2] = {nullptr, nullptr};  // normal | t
-  uint32_t* d_id[2] = {nullptr, nullptr};   // BVH record, all ones for a miss
+  DevPtr<float4> d_color[2];  // rgb | N
+  DevPtr<float4> d_guide[2];  // normal | t
+  DevPtr<uint32_t> d_id[2];   // BVH record, all ones for a miss
   srt_temporal_params params;
   srt::temporal::History hist;
   srt::temporal::Poses poses;
-  uint4* d_motion = nullptr;      // one MotionRecord per BVH record; grown by srt_temporal_set_models only
+  DevPtr<uint4> d_motion;         // one MotionRecord per BVH record; grown by srt_temporal_set_models only
   uint32_t motion_capacity = 0;   // records
-  float2* d_moments[2] = {nullptr, nullptr};  // m1 | m2 (include/srt_variance.h); allocated by srt_temporal_enable_moments
+  DevPtr<float2> d_moments[2];    // m1 | m2 (include/srt_variance.h); allocated by srt_temporal_enable_moments
   srt::temporal::Moments moments;
   int last_launches = 0;
 };
 
 namespace {
 
-void FreeAll(srt_temporal* tp) {
-  for (int k = 0; k < 2; ++k) {
-    if (tp->d_color[k]) (void)hipFree(tp->d_color[k]);
-    if (tp->d_guide[k]) (void)hipFree(tp->d_guide[k]);
-    if (tp->d_id[k]) (void)hipFree(tp->d_id[k]);
-    if (tp->d_moments[k]) (void)hipFree(tp->d_moments[k]);
-  }
-  if (tp->d_motion) (void)hipFree(tp->d_motion);
-  if (tp->own_stream && tp->stream) (void)hipStreamDestroy(tp->stream);
-}
-
 int Allocate(srt_temporal* tp) {
-  THIP_OK(hipSetDevice(tp->device));
-  if (!tp->stream) {
-    THIP_OK(hipStreamCreateWithFlags(&tp->stream, hipStreamNonBlocking));
-    tp->own_stream = true;
-  }
-  for (int k = 0; k < 2; ++k) {
-    THIP_OK(hipMalloc(&tp->d_color[k], tp->sizes.color_bytes));
-    THIP_OK(hipMalloc(&tp->d_guide[k], tp->sizes.guide_bytes));
-    THIP_OK(hipMalloc(&tp->d_id[k], tp->sizes.id_bytes));
-  }
+  STAGE_HIP_OK(srt::stage::AllocPair(tp->d_color, tp->sizes.color_bytes));
+  STAGE_HIP_OK(srt::stage::AllocPair(tp->d_guide, tp->sizes.guide_bytes));
+  STAGE_HIP_OK(srt::stage::AllocPair(tp->d_id, tp->sizes.id_bytes));
   return SRT_OK;
 }
 
@@ -84,32 +57,24 @@ int srt_temporal_create(int device, void* stream, int width, int height, srt_tem
                                       : "srt_temporal_create: width and height must be at least 1");
     return rc;
   }
-  srt_temporal* tp = new srt_temporal();
-  tp->device = device;
-  tp->stream = static_cast<hipStream_t>(stream);
+  srt::stage::Owned<srt_temporal> tp(new srt_temporal());
   tp->width = width;
   tp->height = height;
   tp->sizes = sizes;
   tp->params = srt::temporal::DefaultParams();
-  if (int rc = Allocate(tp)) {
-    FreeAll(tp);
-    delete tp;
-    return rc;
-  }
-  *out = tp;
+  if (int rc = tp->Acquire(device, stream)) return rc;
+  if (int rc = Allocate(tp.get())) return rc;
+  *out = tp.release();
   return SRT_OK;
 }
 
 int srt_temporal_destroy(srt_temporal* tp) {
   if (!tp) return SRT_ERR_INVALID;
-  (void)hipSetDevice(tp->device);
-  if (tp->stream) (void)hipStreamSynchronize(tp->stream);
-  FreeAll(tp);
-  delete tp;
+  srt::stage::Destroy()(tp);
   return SRT_OK;
 }
 
-void* srt_temporal_stream(srt_temporal* tp) { return tp ? tp->stream : nullptr; }
+void* srt_temporal_stream(srt_temporal* tp) { return srt::stage::StreamOf(tp); }
 
 int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
   if (!tp || !name || !v) return SRT_ERR_INVALID;
@@ -119,14 +84,11 @@ int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
   else if (n == "max_history") *v = (int)tp->params.max_history;
   else if (n == "history") *v = tp->hist.valid ? 1 : 0;
   else if (n == "frames") *v = (int)tp->hist.frames;
-  else if (n == "scratch.bytes") *v = (int)(tp->sizes.scratch_bytes < 0x7FFFFFFFu ? tp->sizes.scratch_bytes : 0x7FFFFFFFu);
+  else if (n == "scratch.bytes") *v = srt::stage::SaturateInt(tp->sizes.scratch_bytes);
   else if (n == "launches") *v = tp->last_launches;
   else if (n == "models") *v = (int)tp->poses.cur.size();
   else if (n == "models.bytes") *v = (int)(tp->motion_capacity * sizeof(srt::temporal::MotionRecord));
-  else if (n == "moments.bytes") {
-    const size_t b = tp->moments.enabled ? 2 * srt::temporal::MomentBytes(tp->sizes) : 0;
-    *v = (int)(b < 0x7FFFFFFFu ? b : 0x7FFFFFFFu);
-  }
+  else if (n == "moments.bytes") *v = srt::stage::SaturateInt(tp->moments.enabled ? 2 * srt::temporal::MomentBytes(tp->sizes) : 0);
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }
@@ -163,7 +125,7 @@ namespace {
 int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, const srt_hit* guide_dev,
                const srt_temporal_camera* cam, void* out_rgba32f_dev, void* out_moments_dev) {
   if (!tp || !accum_rgba32f_dev || !guide_dev || !cam || !out_rgba32f_dev || frames < 1) return SRT_ERR_INVALID;
-  if (((uintptr_t)accum_rgba32f_dev & 15u) || ((uintptr_t)guide_dev & 15u) || ((uintptr_t)out_rgba32f_dev & 15u)) {
+  if (!Aligned(accum_rgba32f_dev, 16) || !Aligned(guide_dev, 16) || !Aligned(out_rgba32f_dev, 16)) {
     srt::SetError("srt_temporal_accumulate: accum, guide and out must be 16-byte aligned");
     return SRT_ERR_INVALID;
   }
@@ -171,7 +133,7 @@ int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, cons
     srt::SetError("srt_temporal_accumulate: out may not alias the inputs");
     return SRT_ERR_INVALID;
   }
-  THIP_OK(hipSetDevice(tp->device));
+  STAGE_HIP_OK(hipSetDevice(tp->device));
   using namespace srt::temporal;
   TParams kp;
   std::memset(&kp, 0, sizeof kp);
@@ -232,7 +194,7 @@ int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, cons
     else
       hipLaunchKernelGGL(temporal_accumulate_motion_kernel, grid, dim3(kBlock), 0, tp->stream, kp, (const uint4*)tp->d_motion, n);
   }
-  THIP_OK(hipGetLastError());
+  STAGE_HIP_OK(hipGetLastError());
   Advance(&tp->hist, *cam);
   AdvancePoses(&tp->poses);
   AdvanceMoments(&tp->moments, out_moments_dev != nullptr);
@@ -252,18 +214,8 @@ int srt_temporal_accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int
 int srt_temporal_enable_moments(srt_temporal* tp) {
   if (!tp) return SRT_ERR_INVALID;
   if (tp->moments.enabled) return SRT_OK;
-  THIP_OK(hipSetDevice(tp->device));
-  float2* m[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2; ++k) {
-    const hipError_t e = hipMalloc(&m[k], srt::temporal::MomentBytes(tp->sizes));
-    if (e != hipSuccess) {
-      if (m[0]) (void)hipFree(m[0]);
-      srt::SetError(std::string("srt_temporal_enable_moments: hipMalloc: ") + hipGetErrorString(e));
-      return SRT_ERR_HIP;
-    }
-  }
-  tp->d_moments[0] = m[0];
-  tp->d_moments[1] = m[1];
+  STAGE_HIP_OK(hipSetDevice(tp->device));
+  STAGE_HIP_OK(srt::stage::AllocPair(tp->d_moments, srt::temporal::MomentBytes(tp->sizes)));
   srt::temporal::EnableMoments(&tp->moments);
   return SRT_OK;
 }
@@ -275,7 +227,7 @@ int srt_temporal_accumulate_moments(srt_temporal* tp, const void* accum_rgba32f_
     srt::SetError("srt_temporal_accumulate_moments: call srt_temporal_enable_moments first");
     return SRT_ERR_INVALID;
   }
-  if (((uintptr_t)out_moments_dev & 15u) || out_moments_dev == accum_rgba32f_dev || out_moments_dev == (const void*)guide_dev ||
+  if (!Aligned(out_moments_dev, 16) || out_moments_dev == accum_rgba32f_dev || out_moments_dev == (const void*)guide_dev ||
       out_moments_dev == out_rgba32f_dev) {
     srt::SetError("srt_temporal_accumulate_moments: out_moments must be 16-byte aligned and alias no other pointer");
     return SRT_ERR_INVALID;
@@ -296,14 +248,11 @@ int srt_temporal_set_models(srt_temporal* tp, const srt_temporal_model* models, 
     return SRT_ERR_INVALID;
   }
   if (n > tp->motion_capacity) {
-    THIP_OK(hipSetDevice(tp->device));
-    uint4* grown = nullptr;
-    THIP_OK(hipMalloc(&grown, (size_t)n * sizeof(srt::temporal::MotionRecord)));
-    if (tp->d_motion) {
-      (void)hipStreamSynchronize(tp->stream);  // an enqueued frame may still read the old array
-      (void)hipFree(tp->d_motion);
-    }
-    tp->d_motion = grown;
+    STAGE_HIP_OK(hipSetDevice(tp->device));
+    DevPtr<uint4> grown;
+    STAGE_HIP_OK(grown.Alloc((size_t)n * sizeof(srt::temporal::MotionRecord)));
+    if (tp->d_motion) (void)hipStreamSynchronize(tp->stream);  // an enqueued frame may still read the old array
+    tp->d_motion = std::move(grown);
     tp->motion_capacity = n;
   }
   return srt::temporal::SetModels(&tp->poses, models, n);

@@ -9,7 +9,8 @@
 // the image before any of them is tested, so the twelve loads are in flight together; a clamped tap is
 // rejected by its `inside` flag.  A pure gather: no atomics, and it writes the other set of the ping-pong
 // history than the one it reads.
-// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division).
+// The arithmetic is the contract's (fp32, source order, no contraction, correctly rounded division).  The 16-B
+// loads, the hit unpacking, the luminance and the pixel-centre ray are image_device.hpp's, shared with denoise.hpp.
 //
 // Moving models (include/srt_temporal_motion.h): the body is a template with two kernels over it.
 // temporal_accumulate_kernel is the static instance, the code an object without poses has always run.
@@ -24,14 +25,12 @@
 // they were (the additions are all under `if constexpr`).
 #pragma once
 
-#include <hip/hip_runtime.h>
-
+#include "image_device.hpp"
 #include "temporal_host.hpp"
 
 namespace srt {
 namespace temporal {
-
-constexpr uint32_t kMissId = 0xFFFFFFFFu;
+using namespace image;
 
 struct TParams {
   const float4* accum;   // the accumulation image (sum | 1)
@@ -51,27 +50,11 @@ struct TParams {
   float po[3], pf[3], pr[3], pu[3];   // the previous camera: origin, front, right, up
 };
 
-__device__ __forceinline__ bool finite1(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
   return (ax * bx + ay * by) + az * bz;
 }
 
-// A whole 16-B word in one dwordx4: the empty asm makes all four components live, or the compiler splits the
-// load at the component that is tested first (denoise.hpp has the same).
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld16(const float4* p) {
-  v4f v = *reinterpret_cast<const v4f*>(p);
-  asm("" : "+v"(v));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint4 ld16(const uint4* p) {
-  v4u v = *reinterpret_cast<const v4u*>(p);
-  asm("" : "+v"(v));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// A whole 8-B word in one dwordx2, as ld16 above.
+// A whole 8-B word in one dwordx2, as image_device.hpp's ld16.
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 ld8(const float2* p) {
   v2f v = *reinterpret_cast<const v2f*>(p);
@@ -87,8 +70,6 @@ struct MParams {
   int has_prev;      // 0: set `pm` holds no moments of the previous frame
 };
 
-__device__ __forceinline__ float lum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
-
 template <bool MOTION, bool MOMENTS>
 __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* __restrict__ motion, uint32_t n_motion,
                                                  const MParams mp) {
@@ -99,9 +80,9 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
   const float4 acc = ld16(tp.accum + pi);
   const uint4 h0 = ld16(tp.hits + 2 * (size_t)pi), h1 = ld16(tp.hits + 2 * (size_t)pi + 1);  // triangle t n.x n.y | n.z material bvh pad
   const float cx = acc.x / tp.frames, cy = acc.y / tp.frames, cz = acc.z / tp.frames;
-  const uint32_t id = h0.x == kMissId ? kMissId : h1.z;
-  const float t = __uint_as_float(h0.y);
-  const float nx = __uint_as_float(h0.z), ny = __uint_as_float(h0.w), nz = __uint_as_float(h1.x);
+  const uint32_t id = hit_id(h0, h1);
+  const float4 g0 = hit_guide(h0, h1);
+  const float t = g0.w, nx = g0.x, ny = g0.y, nz = g0.z;
   float4 res = make_float4(cx, cy, cz, 1.0f);
   float L = 0.0f, m1 = 0.0f, m2 = 0.0f, Nm = 1.0f;
   if constexpr (MOMENTS) {
@@ -111,9 +92,9 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
   }
   if (tp.has_prev && id != kMissId) {
     const float fi = (float)i, fj = (float)j;
-    const float dx = ((tp.p00[0] + fi * tp.du[0]) + fj * tp.dv[0]) - tp.o[0];
-    const float dy = ((tp.p00[1] + fi * tp.du[1]) + fj * tp.dv[1]) - tp.o[1];
-    const float dz = ((tp.p00[2] + fi * tp.du[2]) + fj * tp.dv[2]) - tp.o[2];
+    const float dx = pixel_dir(tp.p00[0], tp.du[0], tp.dv[0], tp.o[0], fi, fj);
+    const float dy = pixel_dir(tp.p00[1], tp.du[1], tp.dv[1], tp.o[1], fi, fj);
+    const float dz = pixel_dir(tp.p00[2], tp.du[2], tp.dv[2], tp.o[2], fi, fj);
     float vx, vy, vz;
     if constexpr (MOTION) {
       float x = t * dx + tp.o[0], y = t * dy + tp.o[1], z = t * dz + tp.o[2];
@@ -218,7 +199,7 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
   }
   tp.out[pi] = res;
   tp.ncol[pi] = res;
-  tp.ngd[pi] = make_float4(nx, ny, nz, t);
+  tp.ngd[pi] = g0;
   tp.nid[pi] = id;
   if constexpr (MOMENTS) {
     const float d = m2 - m1 * m1;

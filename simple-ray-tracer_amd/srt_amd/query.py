@@ -13,6 +13,7 @@ import numpy as np
 
 from . import RAY_DTYPE, Scene, _ptr
 from ._lib import check, lib
+from ._stage import _Stage, rays_arg
 
 __all__ = ["Query", "Hits", "HIT_DTYPE", "MISS"]
 
@@ -64,7 +65,7 @@ class Hits:
         return self.raw.cpu().numpy().view(HIT_DTYPE).reshape(-1)
 
 
-class Query:
+class Query(_Stage):
     """A ray-query object over ``scene`` (a :class:`srt_amd.Scene`) on ``device``.
 
     ``stream``: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` handle the queries run on.  With the default
@@ -73,42 +74,13 @@ class Query:
     it behaves as if it ran on the current stream, whichever that is at the time of the call.
     """
 
+    _prefix = "srt_query"
+
     def __init__(self, scene: Scene, device: int = 0, stream=None):
-        self.device = int(device)
-        self._q = None
-        self._ext = None
-        handle = getattr(stream, "cuda_stream", stream)
-        self._own_stream = not handle
-        h = C.c_void_p()
+        super().__init__(device, stream)
         s = scene
-        check(lib().srt_query_create(self.device, C.c_void_p(handle) if handle else None, _ptr(s.bvhs), len(s.bvhs),
-                                     _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
-                                     len(s.verts), C.byref(h)), "srt_query_create")
-        self._q = h
-
-    # -- lifecycle ------------------------------------------------------------
-    def close(self):
-        if self._q is not None:
-            lib().srt_query_destroy(self._q)
-            self._q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def handle(self):
-        if self._q is None:
-            raise RuntimeError("Query is closed")
-        return self._q
+        self._create(_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
+                     len(s.verts))
 
     # -- state ----------------------------------------------------------------
     def set_bvh_count(self, bvh_count: int):
@@ -119,34 +91,9 @@ class Query:
         m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4)).reshape(16)
         check(lib().srt_query_update_model_matrix(self.handle, int(index), _ptr(m)), "srt_query_update_model_matrix")
 
-    def get_int(self, name: str) -> int:
-        v = C.c_int()
-        check(lib().srt_query_get_int(self.handle, name.encode(), C.byref(v)), f"srt_query_get_int({name})")
-        return v.value
-
     # -- queries --------------------------------------------------------------
-    def _ordered(self, torch):
-        """The library's own stream as a torch stream (default-stream mode), else None."""
-        if not self._own_stream:
-            return None
-        if self._ext is None:
-            self._ext = torch.cuda.ExternalStream(int(lib().srt_query_stream(self.handle)), device=self.device)
-        return self._ext
-
-    def _check_rays(self, torch, rays):
-        if (rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
-                or not rays.is_cuda or rays.device.index != self.device):
-            raise ValueError(f"rays must be a contiguous float32 [n, 8] tensor on cuda:{self.device} (srt_ray fields)")
-
-    def _run(self, fn, what, rays, out):
-        import torch
-        ext = self._ordered(torch)
-        cur = torch.cuda.current_stream(self.device) if ext is not None else None
-        if ext is not None:
-            ext.wait_stream(cur)
-        check(fn(self.handle, C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr())), what)
-        if ext is not None:
-            cur.wait_stream(ext)
+    def _trace(self, fn, what, rays, out):
+        self._run(lambda: fn(self.handle, C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr())), what)
         return out
 
     def closest(self, rays):
@@ -158,9 +105,9 @@ class Query:
             hits = self.closest(dev.to(f"cuda:{self.device}"))
             self.synchronize()
             return hits.numpy()
-        self._check_rays(torch, rays)
+        rays_arg(rays, self.device)
         out = torch.empty((rays.shape[0], 8), dtype=torch.int32, device=rays.device)
-        return Hits(self._run(lib().srt_query_closest, "srt_query_closest", rays, out))
+        return Hits(self._trace(lib().srt_query_closest, "srt_query_closest", rays, out))
 
     def occluded(self, rays):
         """1 where some triangle is accepted (the walk stops at the first): a uint8 ``[n]`` device tensor, or
@@ -171,11 +118,6 @@ class Query:
             occ = self.occluded(dev.to(f"cuda:{self.device}"))
             self.synchronize()
             return occ.cpu().numpy()
-        self._check_rays(torch, rays)
+        rays_arg(rays, self.device)
         out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
-        return self._run(lib().srt_query_occluded, "srt_query_occluded", rays, out)
-
-    def synchronize(self):
-        """Wait for the queries enqueued so far."""
-        import torch
-        torch.cuda.ExternalStream(int(lib().srt_query_stream(self.handle) or 0), device=self.device).synchronize()
+        return self._trace(lib().srt_query_occluded, "srt_query_occluded", rays, out)

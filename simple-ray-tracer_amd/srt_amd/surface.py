@@ -14,6 +14,7 @@ import numpy as np
 from . import Scene, _ptr
 from . import _lib
 from ._lib import check, lib
+from ._stage import _Stage, hits_arg, rays_arg
 
 __all__ = ["Surface", "ATTR_DTYPE"]
 
@@ -29,7 +30,7 @@ def _descs(textures):
     return keep, descs
 
 
-class Surface:
+class Surface(_Stage):
     """A surface-attribute object over ``scene`` (a :class:`srt_amd.Scene`) on ``device``.
 
     As ``Compute.bind_scene`` does, a scene with ``sample_textures`` uploads its textures and passes no
@@ -38,45 +39,16 @@ class Surface:
     its own and orders every call with ``torch.cuda.current_stream()`` by events, as :class:`srt_amd.query.Query`.
     """
 
+    _prefix = "srt_surface"
+
     def __init__(self, scene: Scene, device: int = 0, stream=None):
-        self.device = int(device)
-        self._s = None
-        self._ext = None
-        handle = getattr(stream, "cuda_stream", stream)
-        self._own_stream = not handle
-        h = C.c_void_p()
+        super().__init__(device, stream)
         s = scene
         tex = None if s.sample_textures else np.ascontiguousarray(s.tex_albedo, np.float32)
-        check(lib().srt_surface_create(self.device, C.c_void_p(handle) if handle else None, _ptr(s.bvhs), len(s.bvhs),
-                                       _ptr(s.mats), _ptr(tex), len(s.mats), _ptr(s.tris), len(s.tris), _ptr(s.verts),
-                                       len(s.verts), C.byref(h)), "srt_surface_create")
-        self._s = h
+        self._create(_ptr(s.bvhs), len(s.bvhs), _ptr(s.mats), _ptr(tex), len(s.mats), _ptr(s.tris), len(s.tris),
+                     _ptr(s.verts), len(s.verts))
         if s.sample_textures:
             self.upload_textures(s.textures)
-
-    # -- lifecycle ------------------------------------------------------------
-    def close(self):
-        if self._s is not None:
-            lib().srt_surface_destroy(self._s)
-            self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def handle(self):
-        if self._s is None:
-            raise RuntimeError("Surface is closed")
-        return self._s
 
     # -- state ----------------------------------------------------------------
     def upload_textures(self, textures):
@@ -92,45 +64,16 @@ class Surface:
         m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4)).reshape(16)
         check(lib().srt_surface_update_model_matrix(self.handle, int(index), _ptr(m)), "srt_surface_update_model_matrix")
 
-    def get_int(self, name: str) -> int:
-        v = C.c_int()
-        check(lib().srt_surface_get_int(self.handle, name.encode(), C.byref(v)), f"srt_surface_get_int({name})")
-        return v.value
-
     # -- work -----------------------------------------------------------------
-    def _ordered(self, torch):
-        if not self._own_stream:
-            return None
-        if self._ext is None:
-            self._ext = torch.cuda.ExternalStream(int(lib().srt_surface_stream(self.handle)), device=self.device)
-        return self._ext
-
     def shade(self, rays, hits):
         """``rays``: the contiguous float32 ``[n, 8]`` device tensor of ``srt_ray`` records that was traced;
         ``hits``: its :class:`srt_amd.query.Hits` (or their ``[n, 8]`` int32 tensor).  Returns a float32 ``[n, 8]``
         device tensor of ``srt_surface_attr`` records: columns 0-2 albedo, 3 bary_v, 4 bary_w, 5-6 uv, 7 the hit
         flag as bits (``.cpu().numpy().view(ATTR_DTYPE)`` names them)."""
         import torch
-        raw = getattr(hits, "raw", hits)
-        dev = f"cuda:{self.device}"
-        if (rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous()
-                or not rays.is_cuda or rays.device.index != self.device):
-            raise ValueError(f"rays must be a contiguous float32 [n, 8] tensor on {dev} (srt_ray fields)")
-        if (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device or not raw.is_contiguous()
-                or tuple(raw.shape) != (rays.shape[0], 8)):
-            raise ValueError(f"hits must be the [n, 8] int32 srt_hit tensor of the rays on {dev}")
+        rays_arg(rays, self.device)
+        _, raw = hits_arg(hits, rays.shape[0], self.device, text="hits must be the [n, 8] int32 srt_hit tensor of the rays")
         out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
-        ext = self._ordered(torch)
-        cur = torch.cuda.current_stream(self.device) if ext is not None else None
-        if ext is not None:
-            ext.wait_stream(cur)
-        check(lib().srt_surface_shade(self.handle, C.c_void_p(rays.data_ptr()), C.c_void_p(raw.data_ptr()),
-                                      rays.shape[0], C.c_void_p(out.data_ptr())), "srt_surface_shade")
-        if ext is not None:
-            cur.wait_stream(ext)
+        self._run(lambda: lib().srt_surface_shade(self.handle, C.c_void_p(rays.data_ptr()), C.c_void_p(raw.data_ptr()),
+                                                  rays.shape[0], C.c_void_p(out.data_ptr())), "srt_surface_shade")
         return out
-
-    def synchronize(self):
-        """Wait for the work enqueued so far."""
-        import torch
-        torch.cuda.ExternalStream(int(lib().srt_surface_stream(self.handle) or 0), device=self.device).synchronize()

@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import TemporalCamera, TemporalModel, TemporalParams, check, lib
+from ._stage import _Stage, accum_arg, get_params, hits_arg, updated_params
 
 __all__ = ["Temporal"]
 
@@ -31,7 +32,7 @@ def _camera(camera) -> TemporalCamera:
     return TemporalCamera(*[(C.c_float * 3)(*[float(x) for x in v]) for v in vec])
 
 
-class Temporal:
+class Temporal(_Stage):
     """A temporal accumulator for ``width`` x ``height`` frames on ``device``.
 
     ``stream``: a ``torch.cuda.Stream`` or a raw ``hipStream_t`` handle.  With the default (None) the object runs
@@ -39,64 +40,21 @@ class Temporal:
     :class:`srt_amd.denoise.Denoiser` does.
     """
 
+    _prefix = "srt_temporal"
+
     def __init__(self, width: int, height: int, device: int = 0, stream=None):
-        self.width, self.height, self.device = int(width), int(height), int(device)
-        self._d = None
-        self._ext = None
-        handle = getattr(stream, "cuda_stream", stream)
-        self._own_stream = not handle
-        h = C.c_void_p()
-        check(lib().srt_temporal_create(self.device, C.c_void_p(handle) if handle else None, self.width, self.height,
-                                        C.byref(h)), "srt_temporal_create")
-        self._d = h
-
-    # -- lifecycle ------------------------------------------------------------
-    def close(self):
-        if self._d is not None:
-            lib().srt_temporal_destroy(self._d)
-            self._d = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def handle(self):
-        if self._d is None:
-            raise RuntimeError("Temporal is closed")
-        return self._d
+        super().__init__(device, stream)
+        self.width, self.height = int(width), int(height)
+        self._create(self.width, self.height)
 
     # -- state ----------------------------------------------------------------
-    def get_int(self, name: str) -> int:
-        v = C.c_int()
-        check(lib().srt_temporal_get_int(self.handle, name.encode(), C.byref(v)), f"srt_temporal_get_int({name})")
-        return v.value
-
     @property
     def params(self) -> dict:
-        p = TemporalParams()
-        check(lib().srt_temporal_get_params(self.handle, C.byref(p)), "srt_temporal_get_params")
-        return {n: getattr(p, n) for n, _ in TemporalParams._fields_}
+        return get_params(TemporalParams, lib().srt_temporal_get_params, self.handle, "srt_temporal_get_params")
 
     def set_params(self, **kw):
         """Any of max_history, depth_tol, normal_min; the others keep their values."""
-        cur = self.params
-        unknown = set(kw) - set(cur)
-        if unknown:
-            raise TypeError(f"unknown temporal parameter(s): {sorted(unknown)}")
-        cur.update(kw)
-        mh = int(cur["max_history"])
-        if not 0 <= mh <= 0xFFFFFFFF:
-            raise ValueError("max_history must fit an unsigned 32-bit integer")
-        p = TemporalParams(mh, float(cur["depth_tol"]), float(cur["normal_min"]))
+        p = updated_params(TemporalParams, self.params, kw, "temporal")
         check(lib().srt_temporal_set_params(self.handle, C.byref(p)), "srt_temporal_set_params")
 
     def reset(self):
@@ -125,23 +83,6 @@ class Temporal:
         check(lib().srt_temporal_set_models(self.handle, arr, n), "srt_temporal_set_models")
 
     # -- work -----------------------------------------------------------------
-    def _ordered(self, torch):
-        if not self._own_stream:
-            return None
-        if self._ext is None:
-            self._ext = torch.cuda.ExternalStream(int(lib().srt_temporal_stream(self.handle)), device=self.device)
-        return self._ext
-
-    def _run(self, call, what):
-        import torch
-        ext = self._ordered(torch)
-        cur = torch.cuda.current_stream(self.device) if ext is not None else None
-        if ext is not None:
-            ext.wait_stream(cur)
-        check(call(), what)
-        if ext is not None:
-            cur.wait_stream(ext)
-
     def accumulate(self, accum, frames: int, hits, camera):
         """Blend the accumulation image ``accum`` (the SUM over ``frames``: a contiguous float32 ``[H, W, 4]``
         device tensor, or a raw device pointer) into the history.  ``hits``: the guide of ``camera``'s pixel-centre
@@ -149,17 +90,8 @@ class Temporal:
         result ``(colour, N)`` on the device."""
         import torch
         dev = f"cuda:{self.device}"
-        if isinstance(accum, int):
-            acc_ptr, keep = accum, None
-        else:
-            if (accum.dtype != torch.float32 or not accum.is_cuda or accum.device.index != self.device
-                    or not accum.is_contiguous() or accum.numel() != self.width * self.height * 4):
-                raise ValueError(f"accum must be a contiguous float32 [H, W, 4] tensor on {dev}")
-            acc_ptr, keep = accum.data_ptr(), accum
-        raw = getattr(hits, "raw", hits)
-        if raw is None or (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device
-                           or not raw.is_contiguous() or tuple(raw.shape) != (self.width * self.height, 8)):
-            raise ValueError(f"hits must be the [W * H, 8] int32 srt_hit tensor on {dev}")
+        acc_ptr, keep = accum_arg(accum, self.width, self.height, self.device)
+        _, raw = hits_arg(hits, self.width * self.height, self.device)
         cam = _camera(camera)
         out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
         self._run(lambda: lib().srt_temporal_accumulate(self.handle, C.c_void_p(acc_ptr), int(frames),
@@ -178,17 +110,8 @@ class Temporal:
         ``Denoiser.run_variance``.  Needs ``enable_moments()``."""
         import torch
         dev = f"cuda:{self.device}"
-        if isinstance(accum, int):
-            acc_ptr, keep = accum, None
-        else:
-            if (accum.dtype != torch.float32 or not accum.is_cuda or accum.device.index != self.device
-                    or not accum.is_contiguous() or accum.numel() != self.width * self.height * 4):
-                raise ValueError(f"accum must be a contiguous float32 [H, W, 4] tensor on {dev}")
-            acc_ptr, keep = accum.data_ptr(), accum
-        raw = getattr(hits, "raw", hits)
-        if raw is None or (raw.dtype != torch.int32 or not raw.is_cuda or raw.device.index != self.device
-                           or not raw.is_contiguous() or tuple(raw.shape) != (self.width * self.height, 8)):
-            raise ValueError(f"hits must be the [W * H, 8] int32 srt_hit tensor on {dev}")
+        acc_ptr, keep = accum_arg(accum, self.width, self.height, self.device)
+        _, raw = hits_arg(hits, self.width * self.height, self.device)
         cam = _camera(camera)
         out = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
         mom = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=dev)
@@ -198,8 +121,3 @@ class Temporal:
                   "srt_temporal_accumulate_moments")
         del keep
         return out, mom
-
-    def synchronize(self):
-        """Wait for the work enqueued so far."""
-        import torch
-        torch.cuda.ExternalStream(int(lib().srt_temporal_stream(self.handle) or 0), device=self.device).synchronize()
