@@ -1,5 +1,6 @@
-// srt/query.hpp -- header-only C++ mirror of include/srt_query.h: srt::Query, RAII over the C ABI with the
-// same method names.  Errors throw std::runtime_error carrying srt_last_error().
+// srt/query.hpp -- header-only C++ mirror of include/srt_query.h and include/srt_refit.h: srt::Query, RAII over
+// the C ABI with the same method names, and AssetUtils::RefitBVH.  Errors throw std::runtime_error carrying
+// srt_last_error().
 #pragma once
 
 #include <cstdint>
@@ -8,19 +9,22 @@
 #include <utility>
 
 #include "../srt_query.h"
+#include "../srt_refit.h"
 
 namespace srt {
 
 class Query {
  public:
-  // The std430 arrays srt_upload_scene takes; `stream` is a hipStream_t (nullptr: a stream of its own).
+  // The std430 arrays srt_upload_scene takes; `stream` is a hipStream_t (nullptr: a stream of its own);
+  // `flags`: 0, or SRT_QUERY_REFIT for an object Refit() can move to new vertices.
   Query(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes,
-        uint32_t n_nodes, const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts) {
-    Check(srt_query_create(device, stream, bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, &q_),
-          "srt_query_create");
+        uint32_t n_nodes, const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts,
+        uint32_t flags = 0) {
+    Check(srt_query_create_ex(device, stream, bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, flags, &q_),
+          "srt_query_create_ex");
   }
-  Query(int device, void* stream, const srt_scene* scene) {
-    Check(srt_query_create_obj(device, stream, scene, &q_), "srt_query_create_obj");
+  Query(int device, void* stream, const srt_scene* scene, uint32_t flags = 0) {
+    Check(srt_query_create_obj_ex(device, stream, scene, flags, &q_), "srt_query_create_obj_ex");
   }
   ~Query() {
     if (q_) srt_query_destroy(q_);
@@ -40,6 +44,8 @@ class Query {
   void update_model_matrix(uint32_t index, const float frame[16]) {
     Check(srt_query_update_model_matrix(q_, index, frame), "srt_query_update_model_matrix");
   }
+  // srt_query_refit: `verts_dev` is a device array of `n` srt_vertex records; only enqueues on the query's stream.
+  void Refit(const srt_vertex* verts_dev, uint32_t n) { Check(srt_query_refit(q_, verts_dev, n), "srt_query_refit"); }
   // Device pointers; both only enqueue on the query's stream.
   void closest(const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
     Check(srt_query_closest(q_, rays_dev, n, hits_dev), "srt_query_closest");
@@ -62,5 +68,16 @@ class Query {
   }
   srt_query* q_ = nullptr;
 };
+
+namespace AssetUtils {
+
+// srt_bvh_refit: the bounds of every reached node of `nodes`, in place, refit to `verts` (the topology stays).
+inline void RefitBVH(const srt_bvh_record* bvhs, uint32_t n_bvhs, srt_bvh_node* nodes, uint32_t n_nodes,
+                     const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts) {
+  if (int rc = srt_bvh_refit(bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts))
+    throw std::runtime_error("srt_bvh_refit failed with status " + std::to_string(rc) + ": " + srt_last_error());
+}
+
+}  // namespace AssetUtils
 
 }  // namespace srt

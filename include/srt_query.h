@@ -55,7 +55,7 @@ int srt_query_occluded(srt_query* q, const srt_ray* rays_dev, uint32_t n, uint8_
 /* "stack.entries" (tree depth + 1), "stack.in_hbm" (1: the traversal stacks do not fit LDS), "stack.packed"
  * (1: 2-dword entries), "launch.blocks" / "launch.block" (blocks and lanes per block of the last launch),
  * "scratch.bytes" (device scratch the object holds now), "refill.min" (lanes under which a wave refills),
- * "bvh_count".  SRT_ERR_NOT_FOUND for other names. */
+ * "bvh_count"; srt_refit.h adds "refit*" and "layout.*".  SRT_ERR_NOT_FOUND for other names. */
 int srt_query_get_int(srt_query* q, const char* name, int* v);
 void* srt_query_stream(srt_query* q);
 

@@ -10,26 +10,14 @@
 #include <vector>
 
 #include "../../include/srt_query.h"
+#include "../../include/srt_refit.h"
 #include "query.hpp"
 #include "query_host.hpp"
+#include "query_object.hpp"
 #include "stage.hpp"
 
 using srt::stage::Aligned;
 using srt::stage::DevPtr;
-
-struct srt_query : srt::stage::Stage {
-  DevPtr<float4> d_pairs, d_roots, d_tris;
-  DevPtr<float> d_frames;
-  DevPtr<uint32_t> d_ctr;
-  DevPtr<uint32_t> d_stack;  // HBM stacks of `stack_blocks` blocks (deep trees only)
-  int stack_blocks = 0;
-  size_t scene_bytes = 0;
-  uint32_t n_bvhs = 0, bvh_count = 0;
-  srt::query::StackPlan plan;
-  int max_blocks[2] = {0, 0};  // persistent grid of the closest / any instance
-  int refill_min = 0, claim_env = 0;
-  int last_blocks = 0;
-};
 
 namespace {
 
@@ -67,6 +55,9 @@ int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bv
   STAGE_HIP_OK(hipMemcpyAsync(q->d_frames, frames.data(), fb, hipMemcpyHostToDevice, q->stream));
   STAGE_HIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
   q->scene_bytes = pb + rb + tb + fb;
+  q->pairs_bytes = pb;
+  q->roots_bytes = rb;
+  q->tris_bytes = tb;
   // persistent grid: the blocks the device holds at once
   hipDeviceProp_t prop;
   STAGE_HIP_OK(hipGetDeviceProperties(&prop, q->device));
@@ -139,8 +130,18 @@ int srt_query_abi_version(void) { return SRT_QUERY_ABI_VERSION; }
 int srt_query_create(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes,
                      uint32_t n_nodes, const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts,
                      uint32_t n_verts, srt_query** out) {
+  return srt_query_create_ex(device, stream, bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, 0, out);
+}
+
+int srt_query_create_ex(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes,
+                        uint32_t n_nodes, const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts,
+                        uint32_t n_verts, uint32_t flags, srt_query** out) {
   if (!out) return SRT_ERR_INVALID;
   *out = nullptr;
+  if (flags & ~SRT_QUERY_REFIT) {
+    srt::SetError("srt_query_create_ex: unknown flags");
+    return SRT_ERR_INVALID;
+  }
   // host-side validation and re-layout first: a bad scene never reaches the device
   srt::query::Layout lay;
   std::string err;
@@ -166,16 +167,23 @@ int srt_query_create(int device, void* stream, const srt_bvh_record* bvhs, uint3
   q->claim_env = e ? std::max(0, std::min(64, std::atoi(e))) : 0;
   if (int rc = q->Acquire(device, stream)) return rc;
   if (int rc = Upload(q.get(), lay, bvhs)) return rc;
+  if (flags & SRT_QUERY_REFIT)
+    if (int rc = srt::refit::Attach(q.get(), lay, tris, n_tris, n_verts)) return rc;
   *out = q.release();
   return SRT_OK;
 }
 
 int srt_query_create_obj(int device, void* stream, const srt_scene* s, srt_query** out) {
+  return srt_query_create_obj_ex(device, stream, s, 0, out);
+}
+
+int srt_query_create_obj_ex(int device, void* stream, const srt_scene* s, uint32_t flags, srt_query** out) {
   if (!s || !out) return SRT_ERR_INVALID;
   srt::stage::SceneArrays a;
   if (int rc = srt::stage::CopyScene(s, &a)) return rc;
-  return srt_query_create(device, stream, a.bvhs.data(), (uint32_t)a.bvhs.size(), a.nodes.data(), (uint32_t)a.nodes.size(),
-                          a.tris.data(), (uint32_t)a.tris.size(), a.verts.data(), (uint32_t)a.verts.size(), out);
+  return srt_query_create_ex(device, stream, a.bvhs.data(), (uint32_t)a.bvhs.size(), a.nodes.data(),
+                             (uint32_t)a.nodes.size(), a.tris.data(), (uint32_t)a.tris.size(), a.verts.data(),
+                             (uint32_t)a.verts.size(), flags, out);
 }
 
 int srt_query_destroy(srt_query* q) {
@@ -222,6 +230,14 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   else if (n == "scene.bytes") *v = srt::stage::SaturateInt(q->scene_bytes);
   else if (n == "refill.min") *v = q->refill_min;
   else if (n == "bvh_count") *v = (int)q->bvh_count;
+  else if (n == "refit") *v = q->refit ? 1 : 0;
+  else if (n == "refit.heights") *v = (int)q->schedule.heights;
+  else if (n == "refit.launches") *v = (int)q->schedule.launches;
+  else if (n == "refit.bytes") *v = srt::stage::SaturateInt(q->refit_bytes);
+  else if (n == "refit.count") *v = q->refit_count;
+  else if (n == "layout.pairs") *v = srt::stage::SaturateInt(q->pairs_bytes);
+  else if (n == "layout.roots") *v = srt::stage::SaturateInt(q->roots_bytes);
+  else if (n == "layout.tris") *v = srt::stage::SaturateInt(q->tris_bytes);
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }

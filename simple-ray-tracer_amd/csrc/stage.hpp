@@ -1,5 +1,5 @@
-// stage.hpp -- the scaffold the stage objects share (query.hip, denoise.hip, temporal.hip, surface.hip; included by
-// nothing else): the HIP error macro, the device and stream an object runs on, and the ownership of its device
+// stage.hpp -- the scaffold the stage objects share (query.hip, refit.hip, denoise.hip, temporal.hip, surface.hip;
+// included by nothing else): the HIP error macro, the device and stream an object runs on, and the ownership of its device
 // allocations.  The host-only helpers are stage_host.hpp's.
 #pragma once
 

@@ -28,7 +28,7 @@ from . import _lib
 from ._lib import SrtError, check, lib
 
 __all__ = [
-    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "UploadModelDataToGPU",
+    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "UploadModelDataToGPU",
     "UpdateModelMatrix", "Camera", "InputState", "progressive_frame", "PointLight", "generate_noise", "glibc_rand", "SrtError",
     "NODE_DTYPE", "BVH_DTYPE", "MAT_DTYPE", "TRI_DTYPE", "VERT_DTYPE", "LIGHT_DTYPE", "RAY_DTYPE",
     "MODEL_LIGHTS", "SPHERE_LIGHTS", "REFERENCE_OBJECTS",
@@ -345,6 +345,26 @@ class Scene:
         finally:
             lib().srt_scene_free(sh)
         return s
+
+
+def refit_scene(scene: Scene, verts: np.ndarray) -> Scene:
+    """A copy of ``scene`` whose vertices are ``verts`` (a ``VERT_DTYPE`` array, or ``[n_verts, 3]`` positions
+    that keep the scene's uvs) and whose ``nodes`` are refit to them on the host (``srt_bvh_refit``,
+    include/srt_refit.h): the topology stays, every reached node's box follows the new vertices."""
+    import dataclasses
+
+    verts = np.asarray(verts)
+    if verts.dtype != VERT_DTYPE:
+        pos = np.asarray(verts, np.float32).reshape(len(scene.verts), 3)
+        verts = scene.verts.copy()
+        verts["pos"] = pos
+    verts = np.ascontiguousarray(verts).reshape(-1).copy()
+    if len(verts) != len(scene.verts):
+        raise ValueError("refit_scene keeps the number of vertices")
+    nodes = scene.nodes.copy()
+    check(lib().srt_bvh_refit(_ptr(scene.bvhs), len(scene.bvhs), _ptr(nodes), len(nodes), _ptr(scene.tris), len(scene.tris),
+                              _ptr(verts), len(verts)), "srt_bvh_refit")
+    return dataclasses.replace(scene, bvhs=scene.bvhs.copy(), nodes=nodes, verts=verts)
 
 
 # ---------------------------------------------------------------------------

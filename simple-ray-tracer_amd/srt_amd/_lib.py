@@ -202,6 +202,19 @@ _QUERY_SIGS = {
 }
 QUERY_SYMBOLS = tuple(_QUERY_SIGS)
 
+SRT_QUERY_REFIT = 1
+# include/srt_refit.h: BVH refit on the host and of a query object on the device (its own header and version)
+_REFIT_SIGS = {
+    "srt_refit_abi_version": (C.c_int, []),
+    "srt_bvh_refit": (C.c_int, [P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32]),
+    "srt_query_create_ex": (C.c_int, [C.c_int, P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32,
+                                      C.c_uint32, C.POINTER(P)]),
+    "srt_query_create_obj_ex": (C.c_int, [C.c_int, P, P, C.c_uint32, C.POINTER(P)]),
+    "srt_query_refit": (C.c_int, [P, P, C.c_uint32]),
+    "srt_query_copy_layout": (C.c_int, [P, P, P, P]),
+}
+REFIT_SYMBOLS = tuple(_REFIT_SIGS)
+
 
 class DenoiseParams(C.Structure):
     """srt_denoise_params (include/srt_denoise.h)."""
@@ -340,7 +353,7 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
                                   + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
-                                  + list(_SURFACE_SIGS.items())):
+                                  + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

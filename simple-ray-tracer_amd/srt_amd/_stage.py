@@ -4,6 +4,7 @@ is given, and the read-modify-write of a parameter struct."""
 from __future__ import annotations
 
 import ctypes as C
+import gc
 
 from ._lib import check, lib
 
@@ -28,10 +29,15 @@ class _Stage:
     def _fn(self, name):
         return getattr(lib(), f"{self._prefix}_{name}")
 
-    def _create(self, *args):
-        """``<prefix>_create(device, stream, *args, &handle)``."""
+    def _create(self, *args, name="create"):
+        """``<prefix>_<name>(device, stream, *args, &handle)``."""
+        # Device tensors that only unreachable reference cycles still hold (a dead frame kept by its own traceback,
+        # say) are returned now, at the one call of an object's life that allocates, and not at whatever later
+        # moment the collector would pick: a caller who watches torch.cuda.memory_allocated() around the
+        # enqueue-only calls then sees what those calls do, not a collection that happened to fall between them.
+        gc.collect()
         h = C.c_void_p()
-        check(self._fn("create")(self.device, self._stream_arg, *args, C.byref(h)), f"{self._prefix}_create")
+        check(self._fn(name)(self.device, self._stream_arg, *args, C.byref(h)), f"{self._prefix}_{name}")
         self._h = h
 
     # -- lifecycle ------------------------------------------------------------

@@ -11,8 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import RAY_DTYPE, Scene, _ptr
-from ._lib import check, lib
+from . import RAY_DTYPE, VERT_DTYPE, Scene, _ptr
+from ._lib import SRT_QUERY_REFIT, check, lib
 from ._stage import _Stage, rays_arg
 
 __all__ = ["Query", "Hits", "HIT_DTYPE", "MISS"]
@@ -72,15 +72,22 @@ class Query(_Stage):
     (None) the object runs on a stream of its own and orders every call with ``torch.cuda.current_stream()``
     by events -- the call waits for the work already queued there, and that stream waits for the results -- so
     it behaves as if it ran on the current stream, whichever that is at the time of the call.
+
+    ``refit=True`` (``SRT_QUERY_REFIT``, include/srt_refit.h) also uploads the vertex indices and a refit
+    schedule, so :meth:`refit` can move the object to new vertex positions on the device.
     """
 
     _prefix = "srt_query"
 
-    def __init__(self, scene: Scene, device: int = 0, stream=None):
+    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False):
         super().__init__(device, stream)
         s = scene
-        self._create(_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
-                     len(s.verts))
+        args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
+                len(s.verts))
+        if refit:
+            self._create(*args, SRT_QUERY_REFIT, name="create_ex")
+        else:
+            self._create(*args)
 
     # -- state ----------------------------------------------------------------
     def set_bvh_count(self, bvh_count: int):
@@ -90,6 +97,31 @@ class Query(_Stage):
         """``AssetUtils::UpdateModelMatrix``; ``matrix`` is glm column-major (m[c][r])."""
         m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4)).reshape(16)
         check(lib().srt_query_update_model_matrix(self.handle, int(index), _ptr(m)), "srt_query_update_model_matrix")
+
+    # -- refit ----------------------------------------------------------------
+    def refit(self, verts):
+        """Refit the device scene to new vertices (``srt_query_refit``): a contiguous float32 ``[n_verts, 8]``
+        tensor of ``srt_vertex`` records on the object's device -- only enqueued, ordered with the queries as
+        ``closest`` is -- or a numpy ``VERT_DTYPE`` array, which is uploaded first and synchronises."""
+        import torch
+        if isinstance(verts, np.ndarray):
+            host = np.ascontiguousarray(verts, dtype=VERT_DTYPE).view(np.float32).reshape(-1, 8)
+            self.refit(torch.from_numpy(host).to(f"cuda:{self.device}"))
+            self.synchronize()  # the upload may go once the kernels have read it
+            return
+        if (verts.dtype != torch.float32 or not verts.is_cuda or verts.device.index != self.device
+                or not verts.is_contiguous() or verts.dim() != 2 or verts.shape[1] != 8):
+            raise ValueError(f"verts must be a contiguous float32 [n_verts, 8] tensor on cuda:{self.device} "
+                             "(srt_vertex fields)")
+        self._run(lambda: lib().srt_query_refit(self.handle, C.c_void_p(verts.data_ptr()), verts.shape[0]),
+                  "srt_query_refit")
+
+    def layout(self):
+        """The device arrays ``(pairs, roots, tris)`` of csrc/query_host.hpp's layout as uint32 ``[n, 4]`` numpy
+        arrays, one 16-B value a row (``srt_query_copy_layout``: a test and debug readback; synchronises)."""
+        out = [np.zeros((self.get_int("layout." + name) // 16, 4), np.uint32) for name in ("pairs", "roots", "tris")]
+        check(lib().srt_query_copy_layout(self.handle, *[_ptr(a) for a in out]), "srt_query_copy_layout")
+        return tuple(out)
 
     # -- queries --------------------------------------------------------------
     def _trace(self, fn, what, rays, out):

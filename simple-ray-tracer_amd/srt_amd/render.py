@@ -273,6 +273,16 @@ def rubik_model(objects_dir: str | pathlib.Path) -> Model:
     return load_obj(pathlib.Path(objects_dir) / "Rubik" / "Rubik.obj")
 
 
+def wave_vertices(verts: np.ndarray, amplitude: float, phase: float = 0.0) -> np.ndarray:
+    """A ``VERT_DTYPE`` copy of ``verts`` displaced by a sine of each vertex's own position (float32 arithmetic,
+    deterministic): the deformation tools/render.py --wave, tools/bench_refit.py and the refit tests share."""
+    v = verts.copy()
+    p = verts["pos"].astype(np.float32)
+    a, ph = np.float32(amplitude), np.float32(phase)
+    v["pos"] = p + a * np.sin(np.float32(1.7) * p[:, [1, 2, 0]] + np.float32(0.9) * p[:, [2, 0, 1]] + ph).astype(np.float32)
+    return v
+
+
 def splitmix64_uniform(n: int, seed: int = 0x5EED2025) -> np.ndarray:
     """n uniforms in [0, 1) as float32: SplitMix64 stream, top 24 bits * 2^-24."""
     M = np.uint64(0xFFFFFFFFFFFFFFFF)

@@ -2,6 +2,7 @@
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
                               [--max-depth D] [--out frame.png] [--denoise] [--albedo] [--orbit K] [--spin DEG] [--variance]
+                              [--wave A]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -44,7 +45,13 @@ def main():
                     help="with --orbit K (and --spin): the temporal object also integrates luminance moments, and the "
                          "last frame is written a fourth way, <out>_svgf: temporally accumulated, then through the "
                          "variance-guided filter (include/srt_variance.h)")
+    ap.add_argument("--wave", type=float, default=0.0, metavar="A",
+                    help="mesh scenes: displace the model's vertices by a sine of amplitude A before rendering "
+                         "(include/srt_refit.h): the tracer gets the host-refit scene (refit_scene + bind_scene), and with "
+                         "--denoise the guide query is refit on the device (Query(scene, refit=True).refit)")
     a = ap.parse_args()
+    if a.wave and (a.scene == "spheres" or a.orbit or a.albedo):
+        ap.error("--wave A needs a mesh scene, without --orbit and --albedo (surface objects are not refit)")
     if a.albedo and (not a.denoise or a.orbit or a.scene == "spheres"):
         ap.error("--albedo needs --denoise on a mesh scene, without --orbit")
     if a.variance and not a.orbit:
@@ -70,6 +77,12 @@ def main():
         models, show = None, False
     setup = R.make_setup(a.width, a.height, show_model=show, models=models, max_depth=a.max_depth)
     r = R.Renderer(setup)
+    wave_verts = None
+    if a.wave:  # the host half: the same topology, the boxes refit to the displaced vertices, uploaded again
+        import srt_amd as S
+
+        wave_verts = R.wave_vertices(setup.scene.verts, a.wave)
+        r.compute.bind_scene(S.refit_scene(setup.scene, wave_verts))
     if a.orbit:
         try:
             t0 = time.perf_counter()
@@ -88,7 +101,7 @@ def main():
         dt = time.perf_counter() - t0
         r.compute.save_image(a.out)
         if a.denoise:
-            denoised = denoise(r, setup, a.out, a.albedo)
+            denoised = denoise(r, setup, a.out, a.albedo, wave_verts)
     finally:
         r.close()
     print(f"{a.out}: {a.width}x{a.height} @ {a.spp} spp in {dt:.3f} s")
@@ -98,9 +111,11 @@ def main():
             print(f"{denoised[1]}: filtered on albedo-demodulated radiance")
 
 
-def denoise(r, setup, out, albedo=False):
+def denoise(r, setup, out, albedo=False, wave_verts=None):
     """The finished frame of Renderer `r` through srt_amd.denoise.Denoiser, written beside `out`; with `albedo` also
-    through run_albedo on the attrs of srt_amd.surface.Surface.  Returns the paths written."""
+    through run_albedo on the attrs of srt_amd.surface.Surface.  With `wave_verts` (the displaced vertices the frame
+    was rendered with) the guide query is created over the undeformed scene and refit to them on the device.
+    Returns the paths written."""
     import srt_amd as S
     from srt_amd.denoise import Denoiser
     from srt_amd.query import Query
@@ -112,8 +127,10 @@ def denoise(r, setup, out, albedo=False):
     with Denoiser(setup.width, setup.height) as dn:
         hits = None
         if setup.scene is not None:
-            with Query(setup.scene) as q:
+            with Query(setup.scene, refit=wave_verts is not None) as q:
                 q.set_bvh_count(setup.bvh_count)
+                if wave_verts is not None:
+                    q.refit(wave_verts)
                 rays = dn.primary_rays(setup.camera)
                 hits = q.closest(rays)
                 q.synchronize()
