@@ -12,8 +12,10 @@ using namespace dev;
 // BVH traversal (ray_intersects.glsl:49-133), order-exact
 // ---------------------------------------------------------------------------
 // IntersectsBox.  Hardware v_min/v_max (IEEE minNum/maxNum) give the same
-// value as GLSL min/max up to the sign of a zero result, and the result is
-// only ever compared (< dist, isinf), so every decision is unchanged.
+// value as the contract's min/max (the oracle's fmn/fmx) up to the sign of a
+// zero result, and the result is only ever compared (< dist, isinf), so every
+// decision is unchanged.  Checked where NaN terms occur (origins on box
+// planes, zero / infinite / NaN components): tests/test_gpu_special_rays.py.
 __device__ __forceinline__ float box_t(f3 o, f3 inv, float4 lo, float4 hi) {
   const float t0x = (lo.x - o.x) * inv.x, t0y = (lo.y - o.y) * inv.y, t0z = (lo.z - o.z) * inv.z;
   const float t1x = (hi.x - o.x) * inv.x, t1y = (hi.y - o.y) * inv.y, t1z = (hi.z - o.z) * inv.z;
@@ -29,8 +31,10 @@ __device__ __forceinline__ bool box_ok(float b, float dist) { return b < dist &&
 // box_ok(box_t(...), dist) with one compare fewer: `b` receives the entry
 // distance IntersectsBox returns whenever the result is true.  Equivalence:
 // for tn <= tf, b = sel and `sel < dist` already rejects sel = +inf, so only
-// -inf needs its own test; otherwise (tn > tf, or a NaN bound) IntersectsBox
-// returns +inf, which no `< dist` accepts.
+// -inf needs its own test; otherwise (tn > tf, or tn and tf both NaN: each
+// is NaN only when all six terms are) IntersectsBox returns +inf, which no
+// `< dist` accepts.  Checked over every node of Rubik for on-plane rays by
+// tests/test_special_rays_cpu.py::test_three_term_box_test_is_intersects_box.
 __device__ __forceinline__ bool box_test(f3 o, f3 inv, float4 lo, float4 hi, float dist, float& b) {
   const float t0x = (lo.x - o.x) * inv.x, t0y = (lo.y - o.y) * inv.y, t0z = (lo.z - o.z) * inv.z;
   const float t1x = (hi.x - o.x) * inv.x, t1y = (hi.y - o.y) * inv.y, t1z = (hi.z - o.z) * inv.z;
