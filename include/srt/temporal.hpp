@@ -1,4 +1,4 @@
-// srt/temporal.hpp -- header-only C++ mirror of include/srt_temporal.h and include/srt_temporal_motion.h:
+// srt/temporal.hpp -- header-only C++ mirror of include/srt_temporal.h, srt_temporal_motion.h and srt_temporal_deform.h:
 // srt::Temporal, RAII over the C ABI with the same method names.  Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../srt_temporal.h"
+#include "../srt_temporal_deform.h"
 #include "../srt_temporal_motion.h"
 #include "../srt_variance.h"
 
@@ -41,6 +42,14 @@ class Temporal {
   // The pose of BVH records 0..n-1 from now on (srt_temporal_motion.h); n == 0: the static behaviour.
   void SetModels(const srt_temporal_model* models, uint32_t n) {
     Check(srt_temporal_set_models(t_, models, n), "srt_temporal_set_models");
+  }
+  // The mesh whose vertices move (srt_temporal_deform.h): host triangles, read before the call returns; n_tris == 0
+  // detaches.  Then, per frame, the DEVICE vertices the frame was traced against (nullptr: every pixel rigid).
+  void SetMesh(const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts) {
+    Check(srt_temporal_set_mesh(t_, tris, n_tris, n_verts), "srt_temporal_set_mesh");
+  }
+  void SetVertices(const srt_vertex* verts_dev, uint32_t n_verts) {
+    Check(srt_temporal_set_vertices(t_, verts_dev, n_verts), "srt_temporal_set_vertices");
   }
   // world_to_model = frame and its affine inverse.
   static srt_temporal_model ModelFromFrame(const float frame[16]) {

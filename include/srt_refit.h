@@ -13,9 +13,6 @@
  *
  * Out of scope:
  *   - the path tracer's device scene: callers use srt_bvh_refit + srt_upload_scene;
- *   - srt_surface objects, which hold their own copy of the vertices: barycentrics and uv from a deformed
- *     query need a re-created surface object;
- *   - temporal reprojection of deforming surfaces: the history treats them as static or moved by `frame` only;
  *   - rebuilds, topology changes and a changing n_verts;
  *   - motion of lights.
  *

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/srt_surface.h"
+#include "../../include/srt_surface_refit.h"
 #include "stage.hpp"
 #include "surface.hpp"
 #include "surface_host.hpp"
@@ -24,6 +25,9 @@ struct srt_surface : srt::stage::Stage {
   DevPtr<uint4> d_tex_info;
   uint32_t n_bvhs = 0, bvh_count = 0, n_tris = 0, n_tex = 0;
   int last_blocks = 0;
+  DevPtr<uint4> d_triples;  // the triangles' vertex indices: only with SRT_SURFACE_REFIT (include/srt_surface_refit.h)
+  bool refit = false;
+  uint32_t n_verts = 0, refit_count = 0;
 };
 
 namespace {
@@ -72,8 +76,18 @@ int srt_surface_abi_version(void) { return SRT_SURFACE_ABI_VERSION; }
 int srt_surface_create(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_material_obj* mats,
                        const float* tex_albedo, uint32_t n_mats, const srt_triangle* tris, uint32_t n_tris,
                        const srt_vertex* verts, uint32_t n_verts, srt_surface** out) {
+  return srt_surface_create_ex(device, stream, bvhs, n_bvhs, mats, tex_albedo, n_mats, tris, n_tris, verts, n_verts, 0u, out);
+}
+
+int srt_surface_create_ex(int device, void* stream, const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_material_obj* mats,
+                          const float* tex_albedo, uint32_t n_mats, const srt_triangle* tris, uint32_t n_tris,
+                          const srt_vertex* verts, uint32_t n_verts, uint32_t flags, srt_surface** out) {
   if (!out) return SRT_ERR_INVALID;
   *out = nullptr;
+  if (flags & ~SRT_SURFACE_REFIT) {
+    srt::SetError("srt_surface_create_ex: unknown flag");
+    return SRT_ERR_INVALID;
+  }
   // host-side validation and packing first: a bad scene never reaches the device
   srt::surface::Layout lay;
   std::string err;
@@ -85,12 +99,24 @@ int srt_surface_create(int device, void* stream, const srt_bvh_record* bvhs, uin
   s->n_bvhs = s->bvh_count = n_bvhs;
   s->n_tris = n_tris;
   if (int rc = s->Acquire(device, stream)) return rc;
+  if ((flags & SRT_SURFACE_REFIT) && n_tris) {  // ahead of Upload, whose wait for the stream covers this copy too
+    static_assert(sizeof(srt_triangle) == sizeof(uint4), "the index triples are uploaded as they are");
+    const size_t ib = (size_t)n_tris * sizeof(uint4);
+    STAGE_HIP_OK(s->d_triples.Alloc(ib));
+    STAGE_HIP_OK(hipMemcpyAsync(s->d_triples, tris, ib, hipMemcpyHostToDevice, s->stream));
+  }
   if (int rc = Upload(s.get(), lay)) return rc;
+  s->refit = (flags & SRT_SURFACE_REFIT) != 0;
+  s->n_verts = n_verts;
   *out = s.release();
   return SRT_OK;
 }
 
 int srt_surface_create_obj(int device, void* stream, const srt_scene* scene, srt_surface** out) {
+  return srt_surface_create_obj_ex(device, stream, scene, 0u, out);
+}
+
+int srt_surface_create_obj_ex(int device, void* stream, const srt_scene* scene, uint32_t flags, srt_surface** out) {
   if (!scene || !out) return SRT_ERR_INVALID;
   *out = nullptr;
   srt::stage::SceneArrays a;
@@ -110,9 +136,9 @@ int srt_surface_create_obj(int device, void* stream, const srt_scene* scene, srt
     }
   }
   srt_surface* created = nullptr;
-  if (int rc = srt_surface_create(device, stream, a.bvhs.data(), (uint32_t)a.bvhs.size(), a.mats.data(),
-                                  sample ? nullptr : a.tex_albedo.data(), (uint32_t)a.mats.size(), a.tris.data(),
-                                  (uint32_t)a.tris.size(), a.verts.data(), (uint32_t)a.verts.size(), &created))
+  if (int rc = srt_surface_create_ex(device, stream, a.bvhs.data(), (uint32_t)a.bvhs.size(), a.mats.data(),
+                                     sample ? nullptr : a.tex_albedo.data(), (uint32_t)a.mats.size(), a.tris.data(),
+                                     (uint32_t)a.tris.size(), a.verts.data(), (uint32_t)a.verts.size(), flags, &created))
     return rc;
   srt::stage::Owned<srt_surface> s(created);
   if (sample) {
@@ -166,7 +192,37 @@ int srt_surface_get_int(srt_surface* s, const char* name, int* v) {
   else if (n == "launch.block") *v = kBlock;
   else if (n == "textures") *v = srt::stage::SaturateInt(s->n_tex);
   else if (n == "bvh_count") *v = (int)s->bvh_count;
+  else if (n == "refit") *v = s->refit ? 1 : 0;
+  else if (n == "refit.bytes") *v = srt::stage::SaturateInt(s->refit ? (size_t)s->n_tris * sizeof(uint4) : 0);
+  else if (n == "refit.count") *v = (int)s->refit_count;
   else return SRT_ERR_NOT_FOUND;
+  return SRT_OK;
+}
+
+int srt_surface_refit_abi_version(void) { return SRT_SURFACE_REFIT_ABI_VERSION; }
+
+int srt_surface_refit(srt_surface* s, const srt_vertex* verts_dev, uint32_t n_verts) {
+  if (!s) return SRT_ERR_INVALID;
+  if (!s->refit) {
+    srt::SetError("srt_surface_refit: the object was created without SRT_SURFACE_REFIT");
+    return SRT_ERR_INVALID;
+  }
+  if (!verts_dev || !Aligned(verts_dev, 16)) {
+    srt::SetError("srt_surface_refit: verts_dev must be a 16-byte aligned device pointer");
+    return SRT_ERR_INVALID;
+  }
+  if (n_verts != s->n_verts) {
+    srt::SetError("srt_surface_refit: n_verts differs from the count at creation");
+    return SRT_ERR_INVALID;
+  }
+  STAGE_HIP_OK(hipSetDevice(s->device));
+  if (s->n_tris) {
+    const unsigned blocks = (unsigned)(((uint64_t)s->n_tris + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(srt::surface::surface_refit_kernel, dim3(blocks), dim3(kBlock), 0, s->stream, (float4*)s->d_tris,
+                       (const uint4*)s->d_triples, reinterpret_cast<const float4*>(verts_dev), s->n_tris, n_verts);
+    STAGE_HIP_OK(hipGetLastError());
+  }
+  ++s->refit_count;
   return SRT_OK;
 }
 

@@ -124,5 +124,24 @@ __global__ __launch_bounds__(kBlock) void surface_shade_kernel(SParams sp) {
   st16(o + 1, w, s, t, __uint_as_float(1u));
 }
 
+// srt_surface_refit (include/srt_surface_refit.h): one lane per triangle, three 16-B gathers through the index
+// triple, and the record's first three words rewritten -- v0, v1 - v0, v2 - v0, the two subtractions
+// surface_host.cpp's BuildLayout makes; the material index and uv0 of the third word are carried over, the fourth
+// word (uv1 | uv2) is not touched.  `triples` holds n_tris records whose indices srt_surface_create held below n_verts.
+__global__ __launch_bounds__(kBlock) void surface_refit_kernel(float4* __restrict__ tris, const uint4* __restrict__ triples,
+                                                               const float4* __restrict__ verts, uint32_t n_tris,
+                                                               uint32_t n_verts) {
+  const uint32_t t = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if (t >= n_tris) return;
+  const uint4 idx = ld16(triples + t);
+  if (idx.x >= n_verts || idx.y >= n_verts || idx.z >= n_verts) return;  // (validated at creation: never taken)
+  const float4 a = ld16(verts + 2 * (size_t)idx.x), b = ld16(verts + 2 * (size_t)idx.y), c = ld16(verts + 2 * (size_t)idx.z);
+  float4* const o = tris + 4 * (size_t)t;
+  const float4 keep = ld16(o + 2);  // e2.z, material, uv0
+  st16(o, a.x, a.y, a.z, b.x - a.x);
+  st16(o + 1, b.y - a.y, b.z - a.z, c.x - a.x, c.y - a.y);
+  st16(o + 2, c.z - a.z, keep.y, keep.z, keep.w);
+}
+
 }  // namespace surface
 }  // namespace srt

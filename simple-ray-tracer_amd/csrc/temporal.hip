@@ -1,5 +1,6 @@
-// temporal.hip -- the temporal reprojection of include/srt_temporal.h and include/srt_temporal_motion.h: the
-// object, its ping-pong history, the poses' device array and the launches of temporal.hpp's kernels.  A translation unit of its own, as query.hip and denoise.hip are:
+// temporal.hip -- the temporal reprojection of include/srt_temporal.h, include/srt_temporal_motion.h and
+// include/srt_temporal_deform.h: the object, its ping-pong history, the poses' device arrays, the attached mesh and
+// the launches of temporal.hpp's kernels.  A translation unit of its own, as query.hip and denoise.hip are:
 // pathtrace.hip and its headers (the device code srt_code_hash identifies) are only read.
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <string>
 
 #include "../../include/srt_temporal.h"
+#include "../../include/srt_temporal_deform.h"
 #include "../../include/srt_temporal_motion.h"
 #include "../../include/srt_variance.h"
 #include "denoise_host.hpp"
@@ -30,7 +32,13 @@ struct srt_temporal : srt::stage::Stage {
   uint32_t motion_capacity = 0;   // records
   DevPtr<float2> d_moments[2];    // m1 | m2 (include/srt_variance.h); allocated by srt_temporal_enable_moments
   srt::temporal::Moments moments;
+  srt::temporal::Mesh mesh;         // include/srt_temporal_deform.h
+  DevPtr<uint4> d_mesh_tris;        // the triangles' vertex indices; allocated by srt_temporal_set_mesh only
+  DevPtr<float4> d_vprev;           // V': the positions the previous accumulate read
+  DevPtr<uint4> d_deform;           // one DeformRecord per BVH record while a mesh is attached
+  uint32_t deform_capacity = 0;     // records
   int last_launches = 0;
+  int last_deform = 0;
 };
 
 namespace {
@@ -88,6 +96,11 @@ int srt_temporal_get_int(srt_temporal* tp, const char* name, int* v) {
   else if (n == "launches") *v = tp->last_launches;
   else if (n == "models") *v = (int)tp->poses.cur.size();
   else if (n == "models.bytes") *v = (int)(tp->motion_capacity * sizeof(srt::temporal::MotionRecord));
+  else if (n == "mesh.tris") *v = (int)tp->mesh.n_tris;
+  else if (n == "mesh.verts") *v = (int)tp->mesh.n_verts;
+  else if (n == "mesh.bytes")
+    *v = srt::stage::SaturateInt(srt::temporal::MeshBytes(tp->mesh) + (size_t)tp->deform_capacity * sizeof(srt::temporal::DeformRecord));
+  else if (n == "deform") *v = tp->last_deform;
   else if (n == "moments.bytes") *v = srt::stage::SaturateInt(tp->moments.enabled ? 2 * srt::temporal::MomentBytes(tp->sizes) : 0);
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
@@ -114,6 +127,7 @@ int srt_temporal_reset(srt_temporal* tp) {
   srt::temporal::Reset(&tp->hist);
   srt::temporal::ResetPoses(&tp->poses);
   srt::temporal::ResetMoments(&tp->moments);
+  srt::temporal::ResetMesh(&tp->mesh);
   return SRT_OK;
 }
 
@@ -175,7 +189,37 @@ int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, cons
   }
   const uint32_t n = (uint32_t)tp->poses.cur.size();  // <= motion_capacity: srt_temporal_set_models grew the array
   const dim3 grid(tp->sizes.grid_x, tp->sizes.grid_y);
-  if (n == 0) {
+  const bool deform = DeformRuns(tp->mesh);
+  if (deform) {
+    // srt_temporal_set_mesh and srt_temporal_set_models grew d_deform to n records; the chunks travel as the
+    // motion records do.
+    MotionChunk chunk;
+    DeformChunk dchunk;
+    for (uint32_t first = 0; first < n; first += kUploadChunk) {
+      const uint32_t count = FillChunk(tp->poses, first, &chunk);
+      hipLaunchKernelGGL(temporal_motion_upload_kernel, dim3(1), dim3(kUploadLanes), 0, tp->stream, chunk, tp->d_motion, first, count);
+      FillDeformChunk(tp->poses, first, &dchunk);
+      hipLaunchKernelGGL(temporal_deform_upload_kernel, dim3(1), dim3(kDeformUploadLanes), 0, tp->stream, dchunk, tp->d_deform, first,
+                         count);
+    }
+    DParams dp;
+    std::memset(&dp, 0, sizeof dp);
+    dp.tris = tp->d_mesh_tris;
+    dp.verts = static_cast<const float4*>(tp->mesh.verts);
+    dp.vprev = tp->d_vprev;
+    dp.recs = tp->d_deform;
+    dp.n_tris = tp->mesh.n_tris;
+    dp.n_verts = tp->mesh.n_verts;
+    dp.has_vprev = DeformHasPrev(tp->mesh, tp->hist);
+    if (out_moments_dev)
+      hipLaunchKernelGGL(temporal_accumulate_deform_moments_kernel, grid, dim3(kBlock), 0, tp->stream, kp, mp, dp,
+                         (const uint4*)tp->d_motion, n);
+    else
+      hipLaunchKernelGGL(temporal_accumulate_deform_kernel, grid, dim3(kBlock), 0, tp->stream, kp, dp, (const uint4*)tp->d_motion, n);
+    // V becomes V' behind the kernel that read both
+    hipLaunchKernelGGL(temporal_copy_positions_kernel, dim3((dp.n_verts + kBlock - 1) / kBlock), dim3(kBlock), 0, tp->stream, dp.verts,
+                       (float4*)tp->d_vprev, dp.n_verts);
+  } else if (n == 0) {
     if (out_moments_dev)
       hipLaunchKernelGGL(temporal_accumulate_moments_kernel, grid, dim3(kBlock), 0, tp->stream, kp, mp);
     else
@@ -198,7 +242,9 @@ int Accumulate(srt_temporal* tp, const void* accum_rgba32f_dev, int frames, cons
   Advance(&tp->hist, *cam);
   AdvancePoses(&tp->poses);
   AdvanceMoments(&tp->moments, out_moments_dev != nullptr);
-  tp->last_launches = 1 + (int)UploadLaunches(n);
+  AdvanceMesh(&tp->mesh);
+  tp->last_launches = Launches(n, deform);
+  tp->last_deform = deform ? 1 : 0;
   return SRT_OK;
 }
 
@@ -237,6 +283,26 @@ int srt_temporal_accumulate_moments(srt_temporal* tp, const void* accum_rgba32f_
 
 int srt_temporal_motion_abi_version(void) { return SRT_TEMPORAL_MOTION_ABI_VERSION; }
 
+}  // extern "C"
+
+namespace {
+
+// The deform records' array holds a record per pose while a mesh is attached; objects without a mesh have none.
+int GrowDeform(srt_temporal* tp, uint32_t n) {
+  if (tp->mesh.n_tris == 0 || n <= tp->deform_capacity) return SRT_OK;
+  STAGE_HIP_OK(hipSetDevice(tp->device));
+  DevPtr<uint4> grown;
+  STAGE_HIP_OK(grown.Alloc((size_t)n * sizeof(srt::temporal::DeformRecord)));
+  if (tp->d_deform) (void)hipStreamSynchronize(tp->stream);  // an enqueued frame may still read the old array
+  tp->d_deform = std::move(grown);
+  tp->deform_capacity = n;
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int srt_temporal_set_models(srt_temporal* tp, const srt_temporal_model* models, uint32_t n) {
   if (int rc = srt::temporal::ValidateModels(models, n)) {  // before the object or any device is touched
     srt::SetError(rc == SRT_ERR_LIMIT ? "srt_temporal_set_models: more than 65535 records"
@@ -255,7 +321,60 @@ int srt_temporal_set_models(srt_temporal* tp, const srt_temporal_model* models, 
     tp->d_motion = std::move(grown);
     tp->motion_capacity = n;
   }
+  if (int rc = GrowDeform(tp, n)) return rc;
   return srt::temporal::SetModels(&tp->poses, models, n);
+}
+
+int srt_temporal_deform_abi_version(void) { return SRT_TEMPORAL_DEFORM_ABI_VERSION; }
+
+int srt_temporal_set_mesh(srt_temporal* tp, const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts) {
+  static_assert(sizeof(srt_triangle) == sizeof(uint4), "the index triples are uploaded as they are");
+  if (int rc = srt::temporal::ValidateMesh(tris, n_tris, n_verts)) {  // before the object or any device is touched
+    srt::SetError(rc == SRT_ERR_LIMIT ? "srt_temporal_set_mesh: 2^28 triangles or vertices, or more"
+                                      : "srt_temporal_set_mesh: NULL tris or n_verts == 0 with n_tris > 0");
+    return rc;
+  }
+  if (!tp) {
+    srt::SetError("srt_temporal_set_mesh: NULL object");
+    return SRT_ERR_INVALID;
+  }
+  STAGE_HIP_OK(hipSetDevice(tp->device));
+  if (n_tris == 0) {
+    STAGE_HIP_OK(hipStreamSynchronize(tp->stream));  // an enqueued frame may still read the arrays
+    tp->d_mesh_tris = DevPtr<uint4>();
+    tp->d_vprev = DevPtr<float4>();
+    tp->d_deform = DevPtr<uint4>();
+    tp->deform_capacity = 0;
+    return srt::temporal::AttachMesh(&tp->mesh, nullptr, 0, 0);
+  }
+  DevPtr<uint4> idx;  // all, or (freed as they go out of scope) none
+  DevPtr<float4> vprev;
+  const size_t tb = (size_t)n_tris * sizeof(uint4);
+  STAGE_HIP_OK(idx.Alloc(tb));
+  STAGE_HIP_OK(vprev.Alloc((size_t)n_verts * sizeof(float4)));
+  STAGE_HIP_OK(hipMemcpyAsync(idx, tris, tb, hipMemcpyHostToDevice, tp->stream));
+  STAGE_HIP_OK(hipStreamSynchronize(tp->stream));  // `tris` may go; an enqueued frame no longer reads the old arrays
+  tp->d_mesh_tris = std::move(idx);
+  tp->d_vprev = std::move(vprev);
+  if (int rc = srt::temporal::AttachMesh(&tp->mesh, tris, n_tris, n_verts)) return rc;
+  return GrowDeform(tp, (uint32_t)tp->poses.cur.size());
+}
+
+int srt_temporal_set_vertices(srt_temporal* tp, const srt_vertex* verts_dev, uint32_t n_verts) {
+  if (!Aligned(verts_dev, 16)) {
+    srt::SetError("srt_temporal_set_vertices: verts_dev must be 16-byte aligned");
+    return SRT_ERR_INVALID;
+  }
+  if (!tp) {
+    srt::SetError("srt_temporal_set_vertices: NULL object");
+    return SRT_ERR_INVALID;
+  }
+  if (int rc = srt::temporal::SetVertices(&tp->mesh, verts_dev, n_verts)) {
+    srt::SetError(tp->mesh.n_tris == 0 ? "srt_temporal_set_vertices: no mesh attached (srt_temporal_set_mesh)"
+                                       : "srt_temporal_set_vertices: n_verts differs from the mesh's");
+    return rc;
+  }
+  return SRT_OK;
 }
 
 int srt_temporal_model_from_frame(const float frame[16], srt_temporal_model* out) {

@@ -23,6 +23,13 @@
 // history (m1, m2) as one 8-B word per pixel.  The four extra tap loads are issued with the twelve, ahead of the
 // single wait ladder, and accumulate with the colour's weights; the two instances without moments are the code
 // they were (the additions are all under `if constexpr`).
+//
+// Deforming meshes (include/srt_temporal_deform.h): a third template parameter adds, to the two motion instances,
+// the triangle's index triple and its three positions in V (the caller's vertices) and in V' (the object's copy of
+// the previous frame's), and moves a pixel whose triangle changed to the same barycentric point at the previous
+// positions.  The whole addition is one `if constexpr (DEFORM)` block; the four kernels without it are the code
+// they were.  temporal_copy_positions_kernel makes V' of V behind the kernel; temporal_deform_upload_kernel
+// writes the 96-B DeformRecords as temporal_motion_upload_kernel writes the MotionRecords.
 #pragma once
 
 #include "image_device.hpp"
@@ -70,9 +77,26 @@ struct MParams {
   int has_prev;      // 0: set `pm` holds no moments of the previous frame
 };
 
-template <bool MOTION, bool MOMENTS>
+// The deforming mesh of include/srt_temporal_deform.h, next to TParams and MParams (whose layouts stay).
+struct DParams {
+  const uint4* tris;     // v0, v1, v2, material per triangle
+  const float4* verts;   // V: 2 float4 per srt_vertex, the first holds the position
+  const float4* vprev;   // V': 1 float4 per vertex
+  const uint4* recs;     // 6 uint4 per BVH record (DeformRecord), n_motion of them; not read when n_motion == 0
+  uint32_t n_tris, n_verts;
+  int has_vprev;         // 0: every pixel is RIGID (V' holds nothing, or there is no history)
+};
+
+// Position `i` of V (stride 2 words) or V' (stride 1): the first 16 B of the record from an index clamped into the
+// array; the caller zeroes what an index past the array read.
+__device__ __forceinline__ float4 ld_pos(const float4* a, uint32_t i, uint32_t n, uint32_t stride) {
+  return ld16(a + (size_t)stride * (i < n ? i : 0u));
+}
+
+template <bool MOTION, bool MOMENTS, bool DEFORM = false>
 __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* __restrict__ motion, uint32_t n_motion,
-                                                 const MParams mp) {
+                                                 const MParams mp, const DParams dp = DParams()) {
+  static_assert(MOTION || !DEFORM, "a deform instance is a motion instance");
   const int i = (int)blockIdx.x * kRowW + ((int)threadIdx.x & (kRowW - 1));
   const int j = (int)blockIdx.y * kRowH + (int)threadIdx.x / kRowW;
   if (i >= tp.W || j >= tp.H) return;
@@ -96,7 +120,79 @@ __device__ __forceinline__ void accumulate_pixel(const TParams tp, const uint4* 
     const float dy = pixel_dir(tp.p00[1], tp.du[1], tp.dv[1], tp.o[1], fi, fj);
     const float dz = pixel_dir(tp.p00[2], tp.du[2], tp.dv[2], tp.o[2], fi, fj);
     float vx, vy, vz;
-    if constexpr (MOTION) {
+    if constexpr (DEFORM) {
+      float x = t * dx + tp.o[0], y = t * dy + tp.o[1], z = t * dz + tp.o[2];
+      const bool posed = id < n_motion;  // without poses `motion` and `dp.recs` are not read
+      // The loads first: the record's ten words, the triangle's indices, then the six positions behind them.
+      uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0, r2 = r0, r3 = r0, w0 = r0, w1 = r0, w2 = r0, a0 = r0, a1 = r0, a2 = r0;
+      if (posed) {
+        const uint4* rec = motion + 4 * (size_t)id;
+        const uint4* drec = dp.recs + 6 * (size_t)id;
+        r0 = ld16(rec), r1 = ld16(rec + 1), r2 = ld16(rec + 2), r3 = ld16(rec + 3);
+        w0 = ld16(drec), w1 = ld16(drec + 1), w2 = ld16(drec + 2);
+        a0 = ld16(drec + 3), a1 = ld16(drec + 4), a2 = ld16(drec + 5);
+      }
+      bool deforming = false;
+      if (dp.has_vprev) {  // (uniform)
+        const uint32_t k = h0.x;  // a hit's triangle; past the mesh: RIGID, and triangle 0 is loaded and not used
+        const bool in_mesh = k < dp.n_tris;
+        const uint4 idx = ld16(dp.tris + (in_mesh ? k : 0u));
+        float4 p0 = ld_pos(dp.verts, idx.x, dp.n_verts, 2u), p1 = ld_pos(dp.verts, idx.y, dp.n_verts, 2u),
+               p2 = ld_pos(dp.verts, idx.z, dp.n_verts, 2u);
+        float4 q0 = ld_pos(dp.vprev, idx.x, dp.n_verts, 1u), q1 = ld_pos(dp.vprev, idx.y, dp.n_verts, 1u),
+               q2 = ld_pos(dp.vprev, idx.z, dp.n_verts, 1u);
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (idx.x >= dp.n_verts) p0 = q0 = zero;  // the refit's rule for an index past the array
+        if (idx.y >= dp.n_verts) p1 = q1 = zero;
+        if (idx.z >= dp.n_verts) p2 = q2 = zero;
+        const bool same = __float_as_uint(p0.x) == __float_as_uint(q0.x) && __float_as_uint(p0.y) == __float_as_uint(q0.y) &&
+                          __float_as_uint(p0.z) == __float_as_uint(q0.z) && __float_as_uint(p1.x) == __float_as_uint(q1.x) &&
+                          __float_as_uint(p1.y) == __float_as_uint(q1.y) && __float_as_uint(p1.z) == __float_as_uint(q1.z) &&
+                          __float_as_uint(p2.x) == __float_as_uint(q2.x) && __float_as_uint(p2.y) == __float_as_uint(q2.y) &&
+                          __float_as_uint(p2.z) == __float_as_uint(q2.z);
+        if (in_mesh && !same) {  // DEFORMING: the same barycentric point of the triangle as it stood in V'
+          deforming = true;
+          float xm = x, ym = y, zm = z;
+          if (posed) {
+            xm = ((__uint_as_float(w0.x) * x + __uint_as_float(w0.y) * y) + __uint_as_float(w0.z) * z) + __uint_as_float(w0.w);
+            ym = ((__uint_as_float(w1.x) * x + __uint_as_float(w1.y) * y) + __uint_as_float(w1.z) * z) + __uint_as_float(w1.w);
+            zm = ((__uint_as_float(w2.x) * x + __uint_as_float(w2.y) * y) + __uint_as_float(w2.z) * z) + __uint_as_float(w2.w);
+          }
+          const float e1x = p1.x - p0.x, e1y = p1.y - p0.y, e1z = p1.z - p0.z;
+          const float e2x = p2.x - p0.x, e2y = p2.y - p0.y, e2z = p2.z - p0.z;
+          const float px = xm - p0.x, py = ym - p0.y, pz = zm - p0.z;
+          const float d00 = dot3(e1x, e1y, e1z, e1x, e1y, e1z), d01 = dot3(e1x, e1y, e1z, e2x, e2y, e2z);
+          const float d11 = dot3(e2x, e2y, e2z, e2x, e2y, e2z);
+          const float d20 = dot3(px, py, pz, e1x, e1y, e1z), d21 = dot3(px, py, pz, e2x, e2y, e2z);
+          const float denom = 1.0f / (d00 * d11 - d01 * d01);
+          const float bv = (d11 * d20 - d01 * d21) * denom;
+          const float bw = (d00 * d21 - d01 * d20) * denom;
+          const float bu = (1.0f - bv) - bw;
+          const float yx = (bu * q0.x + bv * q1.x) + bw * q2.x;
+          const float yy = (bu * q0.y + bv * q1.y) + bw * q2.y;
+          const float yz = (bu * q0.z + bv * q1.z) + bw * q2.z;
+          x = yx;
+          y = yy;
+          z = yz;
+          if (posed) {
+            x = ((__uint_as_float(a0.x) * yx + __uint_as_float(a0.y) * yy) + __uint_as_float(a0.z) * yz) + __uint_as_float(a0.w);
+            y = ((__uint_as_float(a1.x) * yx + __uint_as_float(a1.y) * yy) + __uint_as_float(a1.z) * yz) + __uint_as_float(a1.w);
+            z = ((__uint_as_float(a2.x) * yx + __uint_as_float(a2.y) * yy) + __uint_as_float(a2.z) * yz) + __uint_as_float(a2.w);
+          }
+        }
+      }
+      if (!deforming && posed && r3.x != 0u) {  // RIGID and MOVING: x' = M_r x, as the motion instance
+        const float mx = ((__uint_as_float(r0.x) * x + __uint_as_float(r0.y) * y) + __uint_as_float(r0.z) * z) + __uint_as_float(r0.w);
+        const float my = ((__uint_as_float(r1.x) * x + __uint_as_float(r1.y) * y) + __uint_as_float(r1.z) * z) + __uint_as_float(r1.w);
+        const float mz = ((__uint_as_float(r2.x) * x + __uint_as_float(r2.y) * y) + __uint_as_float(r2.z) * z) + __uint_as_float(r2.w);
+        x = mx;
+        y = my;
+        z = mz;
+      }
+      vx = x - tp.po[0];
+      vy = y - tp.po[1];
+      vz = z - tp.po[2];
+    } else if constexpr (MOTION) {
       float x = t * dx + tp.o[0], y = t * dy + tp.o[1], z = t * dz + tp.o[2];
       // id is a hit's record here (the miss id was tested above); a record past the poses is STATIC
       const bool posed = id < n_motion;
@@ -227,6 +323,44 @@ __global__ __launch_bounds__(kBlock) void temporal_accumulate_motion_moments_ker
                                                                                     const uint4* __restrict__ motion,
                                                                                     uint32_t n_motion) {
   accumulate_pixel<true, true>(tp, motion, n_motion, mp);
+}
+
+// The two deform instances (include/srt_temporal_deform.h): the motion instances with the mesh's gathers.  `motion`
+// and `dp.recs` hold n_motion records and are not read when it is 0; dp.tris, dp.verts and dp.vprev hold
+// dp.n_tris >= 1, dp.n_verts >= 1 and dp.n_verts entries.
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_deform_kernel(TParams tp, DParams dp,
+                                                                            const uint4* __restrict__ motion,
+                                                                            uint32_t n_motion) {
+  accumulate_pixel<true, false, true>(tp, motion, n_motion, MParams(), dp);
+}
+
+__global__ __launch_bounds__(kBlock) void temporal_accumulate_deform_moments_kernel(TParams tp, MParams mp, DParams dp,
+                                                                                    const uint4* __restrict__ motion,
+                                                                                    uint32_t n_motion) {
+  accumulate_pixel<true, true, true>(tp, motion, n_motion, mp, dp);
+}
+
+// V' = the positions of V: one lane per vertex, one 16-B load and one 16-B vector store.
+__global__ __launch_bounds__(kBlock) void temporal_copy_positions_kernel(const float4* __restrict__ verts,
+                                                                         float4* __restrict__ vprev, uint32_t n_verts) {
+  const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+  if (i >= n_verts) return;
+  const float4 p = ld16(verts + 2 * (size_t)i);
+  v4f v = {p.x, p.y, p.z, p.w};
+  *reinterpret_cast<v4f*>(vprev + i) = v;
+}
+
+// One block of kDeformUploadLanes lanes: lane k stores 16-B word k of the chunk, six words a record, records
+// [first, first + count) of `dst` (count <= kUploadChunk; the host has checked first + count against the capacity).
+constexpr int kDeformUploadLanes = (int)kUploadChunk * 6;
+__global__ __launch_bounds__(kDeformUploadLanes) void temporal_deform_upload_kernel(DeformChunk chunk, uint4* __restrict__ dst,
+                                                                                    uint32_t first, uint32_t count) {
+  const uint32_t k = threadIdx.x;
+  if (k >= count * 6u) return;
+  const DeformRecord& r = chunk.r[k / 6u];
+  const uint32_t w = k % 6u;
+  const float* m = (w < 3u ? r.w2m : r.a) + 4 * (w % 3u);
+  dst[6 * (size_t)first + k] = make_uint4(__float_as_uint(m[0]), __float_as_uint(m[1]), __float_as_uint(m[2]), __float_as_uint(m[3]));
 }
 
 // One block of kUploadLanes lanes: lane k stores 16-B word k of the chunk, records [first, first + count) of `dst`

@@ -149,6 +149,68 @@ void ResetPoses(Poses* p) {
   p->prev.clear();
 }
 
+// ---- deforming meshes ----
+
+int ValidateMesh(const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts) {
+  if (n_tris >= kMaxMesh || n_verts >= kMaxMesh) return SRT_ERR_LIMIT;
+  if (n_tris && (!tris || n_verts == 0)) return SRT_ERR_INVALID;
+  return SRT_OK;
+}
+
+int AttachMesh(Mesh* m, const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts) {
+  if (int rc = ValidateMesh(tris, n_tris, n_verts)) return rc;
+  if (!m) return SRT_ERR_INVALID;
+  *m = Mesh();
+  if (n_tris) {
+    m->n_tris = n_tris;
+    m->n_verts = n_verts;
+  }
+  return SRT_OK;
+}
+
+int SetVertices(Mesh* m, const void* verts_dev, uint32_t n_verts) {
+  if (reinterpret_cast<uintptr_t>(verts_dev) % 16 != 0) return SRT_ERR_INVALID;
+  if (!m || m->n_tris == 0 || n_verts != m->n_verts) return SRT_ERR_INVALID;
+  m->verts = verts_dev;
+  if (!verts_dev) m->has_prev = false;
+  return SRT_OK;
+}
+
+void AdvanceMesh(Mesh* m) {
+  if (DeformRuns(*m)) m->has_prev = true;
+}
+
+void ResetMesh(Mesh* m) {
+  m->has_prev = false;
+}
+
+namespace {
+
+// rows of a column-major affine matrix: row i = (a[i], a[4 + i], a[8 + i], a[12 + i])
+void Rows(const float a[16], float rows[12]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) rows[4 * i + j] = a[4 * j + i];
+}
+
+}  // namespace
+
+DeformRecord DeformOf(const Poses& p, uint32_t r) {
+  DeformRecord rec;
+  std::memset(&rec, 0, sizeof rec);
+  if (r >= p.cur.size()) return rec;
+  Rows(p.cur[r].world_to_model, rec.w2m);
+  Rows(r < p.prev.size() ? p.prev[r].model_to_world : p.cur[r].model_to_world, rec.a);
+  return rec;
+}
+
+uint32_t FillDeformChunk(const Poses& p, uint32_t first, DeformChunk* out) {
+  std::memset(out, 0, sizeof *out);
+  const uint32_t n = (uint32_t)p.cur.size();
+  uint32_t k = 0;
+  for (; k < kUploadChunk && first + k < n; ++k) out->r[k] = DeformOf(p, first + k);
+  return k;
+}
+
 // ---- luminance moments ----
 
 void EnableMoments(Moments* m) {

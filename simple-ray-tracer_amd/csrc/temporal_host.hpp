@@ -1,7 +1,8 @@
 // temporal_host.hpp -- host-only parts of the temporal reprojection (include/srt_temporal.h): parameter
 // validation, buffer sizing, the launch grid and the ping-pong state of the history, and the pose bookkeeping
-// of include/srt_temporal_motion.h.  No device, no HIP header: tests/cpp/test_temporal_host.cpp and
-// tests/cpp/test_temporal_motion_host.cpp link temporal_host.cpp alone.
+// of include/srt_temporal_motion.h and the mesh bookkeeping of include/srt_temporal_deform.h.  No device, no HIP
+// header: tests/cpp/test_temporal_host.cpp, tests/cpp/test_temporal_motion_host.cpp and
+// tests/cpp/test_temporal_deform_host.cpp link temporal_host.cpp alone.
 #pragma once
 
 #include <cstddef>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "../../include/srt_temporal.h"
+#include "../../include/srt_temporal_deform.h"
 #include "../../include/srt_temporal_motion.h"
 
 namespace srt {
@@ -88,6 +90,52 @@ inline uint32_t UploadLaunches(uint32_t n) { return (n + kUploadChunk - 1) / kUp
 // After a call was enqueued: Q becomes P.  With the history's Reset: P is dropped, Q stays.
 void AdvancePoses(Poses* p);
 void ResetPoses(Poses* p);
+
+// ---- deforming meshes (include/srt_temporal_deform.h) ----
+
+constexpr uint32_t kMaxMesh = SRT_TEMPORAL_MAX_MESH;
+
+// SRT_OK; SRT_ERR_LIMIT for a count >= kMaxMesh; SRT_ERR_INVALID for NULL `tris` or n_verts == 0 with n_tris > 0.
+// The counts are checked before the array.
+int ValidateMesh(const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts);
+
+// The attached mesh, V (the caller's device array; only its address is held here) and whether V' -- the object's
+// copy of the positions the previous accumulate read -- holds any.
+struct Mesh {
+  uint32_t n_tris = 0, n_verts = 0;  // n_tris == 0: no mesh
+  const void* verts = nullptr;       // V
+  bool has_prev = false;             // V' is valid
+};
+// ValidateMesh, then the counts; V and V' are dropped.  n_tris == 0 detaches.
+int AttachMesh(Mesh* m, const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts);
+// srt_temporal_set_vertices on an existing object: SRT_ERR_INVALID (state unchanged) for a pointer that is not
+// 16-B aligned, no mesh, or n_verts != the mesh's.  NULL drops V and V'.
+int SetVertices(Mesh* m, const void* verts_dev, uint32_t n_verts);
+// Whether the accumulate about to be enqueued runs a deform instance, and whether that instance finds V'.
+inline bool DeformRuns(const Mesh& m) { return m.n_tris > 0 && m.verts != nullptr; }
+inline int DeformHasPrev(const Mesh& m, const History& h) { return DeformRuns(m) && m.has_prev && h.valid ? 1 : 0; }
+// After a call was enqueued: a deform instance's copy made V' valid.  With the history's Reset: V' is dropped.
+void AdvanceMesh(Mesh* m);
+void ResetMesh(Mesh* m);
+// Device bytes of the vertex indices and of V' (the deform records are counted by their capacity, next to them).
+inline size_t MeshBytes(const Mesh& m) { return m.n_tris ? ((size_t)m.n_tris + (size_t)m.n_verts) * 16 : 0; }
+
+// What a deform instance reads per BVH record next to its MotionRecord, 96 B: the rows of Q[r].world_to_model,
+// then the rows of A (P[r].model_to_world when r < n_P, else Q[r].model_to_world), row i = M(i, 0..3).
+struct DeformRecord {
+  float w2m[12];
+  float a[12];
+};
+static_assert(sizeof(DeformRecord) == 96, "six 16-B words");
+struct DeformChunk {
+  DeformRecord r[kUploadChunk];
+};
+DeformRecord DeformOf(const Poses& p, uint32_t r);
+// Records [first, first + kUploadChunk) of Q, zero past its end; returns how many are real.
+uint32_t FillDeformChunk(const Poses& p, uint32_t first, DeformChunk* out);
+// Launches of one accumulate with n poses: the kernel and the motion uploads, and for a deform instance the
+// deform records' uploads and the copy of V into V'.
+inline int Launches(uint32_t n, bool deform) { return 1 + (int)UploadLaunches(n) + (deform ? (int)UploadLaunches(n) + 1 : 0); }
 
 // ---- luminance moments (include/srt_variance.h) ----
 

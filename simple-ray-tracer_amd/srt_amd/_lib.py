@@ -275,6 +275,14 @@ _TEMPORAL_MOTION_SIGS = {
 }
 TEMPORAL_MOTION_SYMBOLS = tuple(_TEMPORAL_MOTION_SIGS)
 
+# include/srt_temporal_deform.h: deforming meshes for the temporal reprojection (its own header and version)
+_TEMPORAL_DEFORM_SIGS = {
+    "srt_temporal_deform_abi_version": (C.c_int, []),
+    "srt_temporal_set_mesh": (C.c_int, [P, P, C.c_uint32, C.c_uint32]),
+    "srt_temporal_set_vertices": (C.c_int, [P, P, C.c_uint32]),
+}
+TEMPORAL_DEFORM_SYMBOLS = tuple(_TEMPORAL_DEFORM_SIGS)
+
 
 
 class DenoiseVarParams(C.Structure):
@@ -320,6 +328,17 @@ _SURFACE_SIGS = {
 }
 SURFACE_SYMBOLS = tuple(_SURFACE_SIGS)
 
+SRT_SURFACE_REFIT = 1
+# include/srt_surface_refit.h: a surface object that follows moving vertices (its own header and version)
+_SURFACE_REFIT_SIGS = {
+    "srt_surface_refit_abi_version": (C.c_int, []),
+    "srt_surface_create_ex": (C.c_int, [C.c_int, P, P, C.c_uint32, P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32,
+                                        C.c_uint32, C.POINTER(P)]),
+    "srt_surface_create_obj_ex": (C.c_int, [C.c_int, P, P, C.c_uint32, C.POINTER(P)]),
+    "srt_surface_refit": (C.c_int, [P, P, C.c_uint32]),
+}
+SURFACE_REFIT_SYMBOLS = tuple(_SURFACE_REFIT_SIGS)
+
 _lib = None
 
 
@@ -353,7 +372,8 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
                                   + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
-                                  + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())):
+                                  + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
+                                  + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -141,6 +141,14 @@ def rays_arg(rays, device):
     return rays.data_ptr(), rays
 
 
+def verts_arg(verts, device):
+    """A contiguous float32 ``[n_verts, 8]`` tensor of ``srt_vertex`` records on ``cuda:device``."""
+    import torch
+    if not _on_device(verts, torch.float32, device) or verts.dim() != 2 or verts.shape[1] != 8:
+        raise ValueError(f"verts must be a contiguous float32 [n_verts, 8] tensor on cuda:{device} (srt_vertex fields)")
+    return verts.data_ptr(), verts
+
+
 # -- parameter structs ---------------------------------------------------------------------------------------------
 def get_params(struct, getter, handle, what) -> dict:
     p = struct()

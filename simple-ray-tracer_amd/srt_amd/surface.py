@@ -14,7 +14,8 @@ import numpy as np
 from . import Scene, _ptr
 from . import _lib
 from ._lib import check, lib
-from ._stage import _Stage, hits_arg, rays_arg
+from ._lib import SRT_SURFACE_REFIT
+from ._stage import _Stage, hits_arg, rays_arg, verts_arg
 
 __all__ = ["Surface", "ATTR_DTYPE"]
 
@@ -41,12 +42,16 @@ class Surface(_Stage):
 
     _prefix = "srt_surface"
 
-    def __init__(self, scene: Scene, device: int = 0, stream=None):
+    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False):
         super().__init__(device, stream)
         s = scene
         tex = None if s.sample_textures else np.ascontiguousarray(s.tex_albedo, np.float32)
-        self._create(_ptr(s.bvhs), len(s.bvhs), _ptr(s.mats), _ptr(tex), len(s.mats), _ptr(s.tris), len(s.tris),
-                     _ptr(s.verts), len(s.verts))
+        args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.mats), _ptr(tex), len(s.mats), _ptr(s.tris), len(s.tris),
+                _ptr(s.verts), len(s.verts))
+        if refit:
+            self._create(*args, SRT_SURFACE_REFIT, name="create_ex")
+        else:
+            self._create(*args)
         if s.sample_textures:
             self.upload_textures(s.textures)
 
@@ -63,6 +68,21 @@ class Surface(_Stage):
         """``AssetUtils::UpdateModelMatrix``; ``matrix`` is glm column-major (m[c][r])."""
         m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(4, 4)).reshape(16)
         check(lib().srt_surface_update_model_matrix(self.handle, int(index), _ptr(m)), "srt_surface_update_model_matrix")
+
+    def refit(self, verts):
+        """Move the object's triangles to new vertices (``srt_surface_refit``, include/srt_surface_refit.h): the
+        contiguous float32 ``[n_verts, 8]`` device tensor of ``srt_vertex`` records ``Query.refit`` takes -- only
+        enqueued, ordered with ``shade`` -- or a numpy ``VERT_DTYPE`` array, which is uploaded first and
+        synchronises.  Needs ``Surface(scene, refit=True)``."""
+        import torch
+        if isinstance(verts, np.ndarray):
+            from . import VERT_DTYPE
+            host = np.ascontiguousarray(verts, dtype=VERT_DTYPE).view(np.float32).reshape(-1, 8)
+            self.refit(torch.from_numpy(host).to(f"cuda:{self.device}"))
+            self.synchronize()  # the upload may go once the kernel has read it
+            return
+        ptr, _ = verts_arg(verts, self.device)
+        self._run(lambda: lib().srt_surface_refit(self.handle, C.c_void_p(ptr), verts.shape[0]), "srt_surface_refit")
 
     # -- work -----------------------------------------------------------------
     def shade(self, rays, hits):

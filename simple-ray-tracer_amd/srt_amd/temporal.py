@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import TemporalCamera, TemporalModel, TemporalParams, check, lib
-from ._stage import _Stage, accum_arg, get_params, hits_arg, updated_params
+from ._stage import _Stage, accum_arg, get_params, hits_arg, updated_params, verts_arg
 
 __all__ = ["Temporal"]
 
@@ -44,6 +44,7 @@ class Temporal(_Stage):
 
     def __init__(self, width: int, height: int, device: int = 0, stream=None):
         super().__init__(device, stream)
+        self._verts = None  # the tensor set_vertices was given
         self.width, self.height = int(width), int(height)
         self._create(self.width, self.height)
 
@@ -81,6 +82,38 @@ class Temporal(_Stage):
             both = np.ascontiguousarray(np.concatenate([f, m], axis=1))
             C.memmove(arr, both.ctypes.data, both.nbytes)
         check(lib().srt_temporal_set_models(self.handle, arr, n), "srt_temporal_set_models")
+
+    def set_mesh(self, scene_or_tris, n_verts=None):
+        """Attach the mesh whose vertices move (include/srt_temporal_deform.h): a :class:`srt_amd.Scene` (its
+        triangles and vertex count), or the ``TRI_DTYPE`` triangle array with ``n_verts``.  ``None`` or an empty
+        array detaches it.  Allocates (the vertex indices and the previous positions) and waits for the stream."""
+        from . import TRI_DTYPE, _ptr
+        if scene_or_tris is None:
+            tris, n_verts = np.zeros(0, TRI_DTYPE), 0
+        elif hasattr(scene_or_tris, "tris"):
+            tris = scene_or_tris.tris
+            n_verts = len(scene_or_tris.verts) if n_verts is None else n_verts
+        else:
+            tris = scene_or_tris
+            if n_verts is None:
+                raise ValueError("set_mesh: n_verts is needed with a triangle array")
+        tris = np.ascontiguousarray(tris, dtype=TRI_DTYPE)
+        self._verts = None
+        check(lib().srt_temporal_set_mesh(self.handle, _ptr(tris) if len(tris) else None, len(tris), int(n_verts)),
+              "srt_temporal_set_mesh")
+
+    def set_vertices(self, verts):
+        """The vertices of the frame about to be accumulated: the contiguous float32 ``[n_verts, 8]`` device tensor
+        ``Query.refit`` was given.  It is kept alive, and applies to every ``accumulate`` until set again; ``None``
+        makes every pixel rigid and drops the previous positions.  Enqueues nothing: the accumulate that reads the
+        array is ordered with ``torch.cuda.current_stream()`` as every call is."""
+        if verts is None:
+            check(lib().srt_temporal_set_vertices(self.handle, None, self.get_int("mesh.verts")), "srt_temporal_set_vertices")
+            self._verts = None
+            return
+        ptr, keep = verts_arg(verts, self.device)
+        check(lib().srt_temporal_set_vertices(self.handle, C.c_void_p(ptr), verts.shape[0]), "srt_temporal_set_vertices")
+        self._verts = keep
 
     # -- work -----------------------------------------------------------------
     def accumulate(self, accum, frames: int, hits, camera):

@@ -7,6 +7,12 @@ the enqueued calls on one stream (--warmup runs unmeasured, median [min, max] of
 srt_denoise_run_albedo and srt_denoise_run with the default parameters, and beside them in the same process a float4
 copy of one frame and the guide (primary rays + srt_query_closest).  Nothing is asserted: this is a measurement tool.
 --out writes the JSON document (profiles/surface.json).
+
+--refit-out (profiles/surface_refit.json) times, per scene, srt_surface_refit (include/srt_surface_refit.h) to waved
+vertices already on the device against what the frame loop had to do without it: destroy the surface object and create
+it again from the host arrays (wall clock, the textures' upload included when the scene samples them).
+--refit-baseline-only times only destroy + create and uses nothing that header added, so the same script run from a
+checkout of the parent commit gives the baseline; --refit-baseline FILE folds that file in.
 """
 from __future__ import annotations
 
@@ -31,9 +37,14 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--scenes", nargs="+", default=["rubik", "airplane_knot"])
     ap.add_argument("--out", help="write the results to this JSON file")
+    ap.add_argument("--refit-out", help="time srt_surface_refit against destroy + create only; write this JSON file")
+    ap.add_argument("--refit-baseline-only", action="store_true", help="with --refit-out: destroy + create only")
+    ap.add_argument("--refit-baseline", help="with --refit-out: a --refit-baseline-only file of the parent commit to fold in")
     a = ap.parse_args()
     if a.warmup < 3 or a.reps < 10:
         ap.error("at least 3 warm-up runs and 10 measured ones")
+    if a.refit_out:
+        return refit_main(a)
     import torch
 
     import bench
@@ -98,6 +109,62 @@ def main():
     if a.out:
         pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         pathlib.Path(a.out).write_text(json.dumps(doc, indent=1) + "\n")
+
+
+def refit_main(a):
+    """--refit-out: see the module docstring."""
+    import statistics
+    import time
+
+    import numpy as np
+    import torch
+
+    import bench
+    from bench_denoise import time_calls
+    from srt_amd import _lib
+    from srt_amd import render as R
+    from srt_amd.surface import Surface
+
+    lib = _lib.lib()
+    doc = {"tool": "tools/bench_surface.py --refit-out", "device": torch.cuda.get_device_name(0),
+           "code_hash": lib.srt_code_hash().decode(), "warmup": a.warmup, "reps": a.reps,
+           "timing": "refit: torch.cuda.Event pairs around the enqueued call, median [min, max] ms; destroy + create: wall "
+                     "clock around close() and Surface(scene), which waits for its uploads, median [min, max] ms",
+           "scenes": []}
+    for name in a.scenes:
+        model = R.rubik_model(ROOT / "tests" / "golden" / "objects") if name == "rubik" else bench.airplane_knot_model()
+        scene = R.make_setup(64, 48, show_model=True, models=[model]).scene
+        r = {"scene": name, "triangles": len(scene.tris), "vertices": len(scene.verts), "sampled_textures": bool(scene.sample_textures)}
+        ms = []
+        surf = Surface(scene)
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            surf.close()
+            surf = Surface(scene)
+            surf.synchronize()
+            if k >= a.warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        surf.close()
+        r["destroy_create_ms"] = [round(statistics.median(ms), 4), round(min(ms), 4), round(max(ms), 4)]
+        if not a.refit_baseline_only:
+            stream = torch.cuda.Stream()
+            with torch.cuda.stream(stream), Surface(scene, stream=stream, refit=True) as s:
+                extent = float(np.ptp(scene.verts["pos"], axis=0).max())
+                v = R.wave_vertices(scene.verts, 0.014 * extent, 0.3)
+                vd = torch.from_numpy(np.ascontiguousarray(v).view(np.float32).reshape(-1, 8)).cuda()
+                r["surface_refit_ms"] = time_calls(torch, lambda: lib.srt_surface_refit(s.handle, C.c_void_p(vd.data_ptr()), len(v)),
+                                                   a.warmup, a.reps)
+                r["refit_bytes"] = s.get_int("refit.bytes")
+        print(json.dumps(r), flush=True)
+        doc["scenes"].append(r)
+    if a.refit_baseline:
+        base = json.loads(pathlib.Path(a.refit_baseline).read_text())
+        doc["parent_commit_baseline"] = {"code_hash": base["code_hash"], "scenes": base["scenes"],
+                                         "what": "the same script with --refit-baseline-only, run in the same session from a "
+                                                 "checkout of the parent commit with its own library"}
+    pathlib.Path(a.refit_out).parent.mkdir(parents=True, exist_ok=True)
+    pathlib.Path(a.refit_out).write_text(json.dumps(doc, indent=1) + "\n")
 
 
 if __name__ == "__main__":

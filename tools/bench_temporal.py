@@ -14,6 +14,14 @@ the same way after the rows above: the call with one pose stated and unchanged (
 launch plus the motion kernel), the call with the cube turned by --spin degrees since the previous frame (guides
 queried under each pose), the static instance once more beside them, and the upload launches by themselves as
 nearly as the interface allows: a 1 x 1 object's call with 0, 1 and 256 poses (its one-pixel kernel is the rest).
+
+--deform-out (profiles/temporal_deform.json) measures the deforming-mesh instances (include/srt_temporal_deform.h) by
+themselves: per scene (Rubik and the 262,144-triangle knot) frames under `wave` with an advancing phase, the guide
+from a refit query per phase; ms per frame of the deform instance without and with moments (each includes its copy of
+V into V'), the copy nearly by itself (a 1 x 1 object's call over the same mesh), and the motion instance on the same
+frames.  --deform-baseline-only writes only the motion-instance rows and uses nothing this header added, so the same
+script run from a checkout of the parent commit gives the baseline; --deform-baseline FILE folds that file in.
+--resource-usage FILE (hipcc -Rpass-analysis=kernel-resource-usage of csrc/temporal.hip) supplies the occupancy.
 """
 from __future__ import annotations
 
@@ -60,9 +68,16 @@ def main():
     ap.add_argument("--out", help="write the results to this JSON file")
     ap.add_argument("--motion-out", help="also time the moving-model instance and write its rows to this JSON file")
     ap.add_argument("--spin", type=float, default=2.0, help="degrees the cube turns per frame in the moving rows")
+    ap.add_argument("--deform-out", help="time the deforming-mesh instances only and write their rows to this JSON file")
+    ap.add_argument("--deform-baseline-only", action="store_true", help="with --deform-out: the motion-instance rows only")
+    ap.add_argument("--deform-baseline", help="with --deform-out: a --deform-baseline-only file of the parent commit to fold in")
+    ap.add_argument("--resource-usage", help="with --deform-out: the compiler's kernel-resource-usage remarks of temporal.hip")
+    ap.add_argument("--wave", type=float, default=0.014, help="--deform-out: the wave's amplitude as a share of the bounds' extent")
     a = ap.parse_args()
     if a.warmup < 3 or a.reps < 10:
         ap.error("at least 3 warm-up runs and 10 measured ones")
+    if a.deform_out:
+        return deform_main(a)
     import torch
 
     from srt_amd import _lib
@@ -211,6 +226,119 @@ def motion_rows(torch, a, doc, setup, q, dn, tp, call, cam0, hits0, time_calls):
                                                                   C.c_void_p(out1.data_ptr())), a.warmup, a.reps)
             out[f"tiny_object_{n_poses}_poses_launches"] = tiny.get_int("launches")
     return out
+
+
+def occupancy_of(path):
+    """{kernel: [VGPRs, waves per SIMD]} of the two deform instances from hipcc's kernel-resource-usage remarks."""
+    import re
+
+    out, name = {}, None
+    for line in pathlib.Path(path).read_text().splitlines():
+        if "Function Name:" in line:
+            m = re.search(r"(temporal_accumulate_\w+?_kernel)E", line)
+            name = m.group(1) if m else None
+        m = re.search(r"\bVGPRs: (\d+)", line)
+        if m and name:
+            out.setdefault(name, [0, 0])[0] = int(m.group(1))
+        m = re.search(r"Occupancy \[waves/SIMD\]: (\d+)", line)
+        if m and name:
+            out.setdefault(name, [0, 0])[1] = int(m.group(1))
+    return {k: v for k, v in out.items() if "deform" in k or "motion" in k}
+
+
+def deform_main(a):
+    """--deform-out: see the module docstring."""
+    import numpy as np
+    import torch
+
+    from srt_amd import _lib
+    from srt_amd import render as R
+    from srt_amd.denoise import Denoiser
+    from srt_amd.query import Query
+    from srt_amd.temporal import Temporal, _camera
+
+    W, H = a.width, a.height
+    lib = _lib.lib()
+    full = not a.deform_baseline_only
+    doc = {"tool": "tools/bench_temporal.py --deform-out", "width": W, "height": H, "device": torch.cuda.get_device_name(0),
+           "code_hash": lib.srt_code_hash().decode(), "warmup": a.warmup, "reps": a.reps, "phase_step": 0.3,
+           "timing": "torch.cuda.Event pairs around the enqueued call on one stream; median [min, max] ms; the previous "
+                     "frame (set_vertices + accumulate at the previous phase) is enqueued before the first event",
+           "scenes": []}
+    ident = np.eye(4, dtype=np.float32).reshape(16)
+    for name in ("rubik", "knot"):
+        model = R.rubik_model(ROOT / "tests" / "golden" / "objects") if name == "rubik" else R.torus_knot_model()
+        setup = R.make_setup(W, H, show_model=True, models=[model])
+        scene = setup.scene
+        extent = float(np.ptp(scene.verts["pos"], axis=0).max())
+        row = {"scene": name, "triangles": len(scene.tris), "vertices": len(scene.verts), "wave_amplitude": round(a.wave * extent, 4)}
+        stream = torch.cuda.Stream()
+        with torch.cuda.stream(stream), Query(scene, stream=stream, refit=True) as q, Denoiser(W, H, stream=stream) as dn, \
+                Temporal(W, H, stream=stream) as tp:
+            q.set_bvh_count(setup.bvh_count)
+            cam = _camera(setup.camera)
+            rays = dn.primary_rays(setup.camera)
+            verts, hits = [], []
+            for k in range(2):
+                v = R.wave_vertices(scene.verts, a.wave * extent, 0.3 * k)
+                verts.append(torch.from_numpy(np.ascontiguousarray(v).view(np.float32).reshape(-1, 8)).cuda())
+                q.refit(verts[-1])
+                hits.append(q.closest(rays))
+            acc = torch.rand((H, W, 4), dtype=torch.float32, device="cuda")
+            out, mom = torch.empty_like(acc), torch.empty_like(acc)
+            row["hit_fraction"] = round(float(hits[1].hit.float().mean()), 4)
+
+            def call(t, k, moments=False):
+                if moments:
+                    return lib.srt_temporal_accumulate_moments(t.handle, C.c_void_p(acc.data_ptr()), 1, C.c_void_p(hits[k].raw.data_ptr()),
+                                                               C.byref(cam), C.c_void_p(out.data_ptr()), C.c_void_p(mom.data_ptr()))
+                return lib.srt_temporal_accumulate(t.handle, C.c_void_p(acc.data_ptr()), 1, C.c_void_p(hits[k].raw.data_ptr()),
+                                                   C.byref(cam), C.c_void_p(out.data_ptr()))
+
+            def reuse():
+                tp.synchronize()
+                return round(float((out[..., 3][hits[1].hit.reshape(H, W)] >= 2).float().mean()), 4)
+
+            tp.enable_moments()
+            tp.set_models([ident])  # one pose, unchanged: the motion instance, every record static
+            for moments, key in ((False, "motion_instance_ms"), (True, "motion_moments_instance_ms")):
+                row[key] = time_calls(torch, lambda: call(tp, 1, moments), a.warmup, a.reps, before=lambda: call(tp, 0, moments))
+            row["motion_instance_launches"] = tp.get_int("launches")
+            row["motion_instance_reuse_fraction_of_hits"] = reuse()
+            if full:
+                tp.set_mesh(scene)
+                for moments, key in ((False, "deform_instance_ms"), (True, "deform_moments_instance_ms")):
+                    def before():
+                        tp.set_vertices(verts[0])
+                        call(tp, 0, moments)
+                        tp.set_vertices(verts[1])
+                    row[key] = time_calls(torch, lambda: call(tp, 1, moments), a.warmup, a.reps, before=before)
+                row["deform_instance_launches"] = tp.get_int("launches")
+                row["deform_instance_reuse_fraction_of_hits"] = reuse()
+                row["mesh_bytes"] = tp.get_int("mesh.bytes")
+                tp.set_vertices(None)
+                with Temporal(1, 1, stream=stream) as tiny:  # a one-pixel kernel and the copy of the whole mesh's positions
+                    a1 = torch.ones((1, 1, 4), dtype=torch.float32, device="cuda")
+                    o1, h1 = torch.empty_like(a1), torch.zeros((1, 8), dtype=torch.int32, device="cuda")
+                    fn = lambda: lib.srt_temporal_accumulate(tiny.handle, C.c_void_p(a1.data_ptr()), 1, C.c_void_p(h1.data_ptr()),  # noqa: E731
+                                                             C.byref(cam), C.c_void_p(o1.data_ptr()))
+                    row["tiny_object_no_mesh_ms"] = time_calls(torch, fn, a.warmup, a.reps)
+                    tiny.set_mesh(scene)
+                    tiny.set_vertices(verts[1])
+                    row["tiny_object_with_copy_ms"] = time_calls(torch, fn, a.warmup, a.reps)
+                    row["copy_bytes"] = 32 * len(scene.verts)
+        print(json.dumps(row), flush=True)
+        doc["scenes"].append(row)
+    if full and a.resource_usage:
+        doc["vgprs_and_waves_per_simd"] = occupancy_of(a.resource_usage)
+        doc["occupancy_source"] = "hipcc -Rpass-analysis=kernel-resource-usage, gfx950"
+    if full and a.deform_baseline:
+        base = json.loads(pathlib.Path(a.deform_baseline).read_text())
+        doc["parent_commit_baseline"] = {"code_hash": base["code_hash"], "scenes": base["scenes"],
+                                         "what": "the same script with --deform-baseline-only, run in the same session from a "
+                                                 "checkout of the parent commit with its own library"}
+    pathlib.Path(a.deform_out).parent.mkdir(parents=True, exist_ok=True)
+    pathlib.Path(a.deform_out).write_text(json.dumps(doc, indent=1) + "\n")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,7 @@
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
                               [--max-depth D] [--out frame.png] [--denoise] [--albedo] [--orbit K] [--spin DEG] [--variance]
-                              [--wave A]
+                              [--wave A [--orbit K [--albedo]]]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -48,12 +48,18 @@ def main():
     ap.add_argument("--wave", type=float, default=0.0, metavar="A",
                     help="mesh scenes: displace the model's vertices by a sine of amplitude A before rendering "
                          "(include/srt_refit.h): the tracer gets the host-refit scene (refit_scene + bind_scene), and with "
-                         "--denoise the guide query is refit on the device (Query(scene, refit=True).refit)")
+                         "--denoise the guide query is refit on the device (Query(scene, refit=True).refit), as is "
+                         "the surface object of --albedo (Surface(scene, refit=True).refit).  With --orbit K the camera "
+                         "stands still and the wave's phase advances by WAVE_PHASE_STEP per frame: each frame's vertices "
+                         "go to the renderer (host refit), the query, the temporal object, whose history follows the "
+                         "surface (include/srt_temporal_deform.h), and with --albedo the surface object")
     a = ap.parse_args()
-    if a.wave and (a.scene == "spheres" or a.orbit or a.albedo):
-        ap.error("--wave A needs a mesh scene, without --orbit and --albedo (surface objects are not refit)")
-    if a.albedo and (not a.denoise or a.orbit or a.scene == "spheres"):
-        ap.error("--albedo needs --denoise on a mesh scene, without --orbit")
+    if a.wave and a.scene == "spheres":
+        ap.error("--wave A needs a mesh scene")
+    if a.wave and a.orbit and a.spin:
+        ap.error("--wave A --orbit K advances the wave under a still camera: without --spin")
+    if a.albedo and (not a.denoise or a.scene == "spheres" or (a.orbit and not a.wave)):
+        ap.error("--albedo needs --denoise on a mesh scene, and with --orbit K also --wave A")
     if a.variance and not a.orbit:
         ap.error("--variance needs --orbit K")
     if a.spin and not a.orbit:
@@ -86,7 +92,7 @@ def main():
     if a.orbit:
         try:
             t0 = time.perf_counter()
-            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance)
+            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance, a.wave, a.albedo)
             dt = time.perf_counter() - t0
         finally:
             r.close()
@@ -135,8 +141,10 @@ def denoise(r, setup, out, albedo=False, wave_verts=None):
                 hits = q.closest(rays)
                 q.synchronize()
             if albedo:
-                with Surface(setup.scene) as surf:
+                with Surface(setup.scene, refit=wave_verts is not None) as surf:
                     surf.set_bvh_count(setup.bvh_count)
+                    if wave_verts is not None:
+                        surf.refit(wave_verts)
                     attrs = surf.shade(rays, hits)
                     surf.synchronize()
                 apath = out.with_name(out.stem + "_albedo_denoised" + out.suffix)
@@ -152,6 +160,7 @@ def denoise(r, setup, out, albedo=False, wave_verts=None):
 
 
 ORBIT_STEP = (0.5, -1.0)  # per frame: MoveRight(0.5), then Rotate(-1 degree of yaw, 0): the camera circles the model
+WAVE_PHASE_STEP = 0.3     # per frame, radians: --wave A --orbit K
 
 
 def spin_frame(scene, degrees):
@@ -168,23 +177,38 @@ def spin_frame(scene, degrees):
     return m.T.reshape(16).astype(np.float32)
 
 
-def orbit(r, setup, frames, spp, out, spin=0.0, variance=False):
+def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False):
     """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
-    (degrees per frame) under a still camera while the first model turns.  Every frame goes through
+    (degrees per frame) under a still camera while the first model turns, or with `wave` (the amplitude) under a
+    still camera while the wave's phase advances -- the per-frame calls of a deforming mesh: the host refit and
+    bind_scene for the renderer, Query.refit, Temporal.set_vertices and, with `albedo`, Surface.refit, whose attrs
+    then demodulate the two filtered images.  Every frame goes through
     srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame raw,
     denoised, and temporally accumulated then denoised, and with `variance` also temporally accumulated then through
     the variance-guided filter (<out>_svgf); returns the paths."""
+    import contextlib
+
+    import numpy as np
+    import torch
+
     import srt_amd as S
     from srt_amd.denoise import Denoiser
     from srt_amd.query import Query
+    from srt_amd.surface import Surface
     from srt_amd.temporal import Temporal
 
     out = pathlib.Path(out)
     paths = [out] + [out.with_name(out.stem + s + out.suffix) for s in ("_denoised", "_temporal") + (("_svgf",) if variance else ())]
     cam, c = setup.camera, r.compute
     acc_ptr, _ = c.image_pointers()
-    with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, Query(setup.scene) as q:
+    with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, \
+            Query(setup.scene, refit=bool(wave)) as q, \
+            (Surface(setup.scene, refit=True) if albedo else contextlib.nullcontext()) as surf:
         q.set_bvh_count(setup.bvh_count)
+        if wave:
+            tp.set_mesh(setup.scene)
+        if albedo:
+            surf.set_bvh_count(setup.bvh_count)
         if variance:
             tp.enable_moments()
             dn.enable_variance()
@@ -194,6 +218,14 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False):
                 S.UpdateModelMatrix(c, 0, frame)
                 q.update_model_matrix(0, frame)
                 tp.set_models([frame])
+            elif wave:  # the per-frame calls of a deforming mesh
+                verts = R.wave_vertices(setup.scene.verts, wave, WAVE_PHASE_STEP * k)
+                c.bind_scene(S.refit_scene(setup.scene, verts))
+                vdev = torch.from_numpy(np.ascontiguousarray(verts).view(np.float32).reshape(-1, 8)).to(f"cuda:{r.compute.device}")
+                q.refit(vdev)
+                tp.set_vertices(vdev)
+                if albedo:
+                    surf.refit(vdev)
             elif k:
                 cam.MoveRight(ORBIT_STEP[0])
                 cam.Rotate(ORBIT_STEP[1], 0.0)
@@ -203,14 +235,20 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False):
                 c.SetVec3("cameraRight", cam.getRightVector())
             r.render(spp)  # clears first: the frame loop resets on any input
             r.finish()
-            hits = q.closest(dn.primary_rays(cam))
+            rays = dn.primary_rays(cam)
+            hits = q.closest(rays)
             if variance:
                 acc, mom = tp.accumulate_moments(acc_ptr, r.accum_frames, hits, cam)
             else:
                 acc = tp.accumulate(acc_ptr, r.accum_frames, hits, cam)
         c.save_image(paths[0])
-        _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
-        _, rgba8_t = dn.run(acc, 1, hits, srgb=True)
+        if albedo:
+            attrs = surf.shade(rays, hits)
+            _, rgba8 = dn.run_albedo(acc_ptr, r.accum_frames, hits, attrs, srgb=True)
+            _, rgba8_t = dn.run_albedo(acc, 1, hits, attrs, srgb=True)
+        else:
+            _, rgba8 = dn.run(acc_ptr, r.accum_frames, hits, srgb=True)
+            _, rgba8_t = dn.run(acc, 1, hits, srgb=True)
         dn.synchronize()
         S.write_image(paths[1], rgba8.cpu().numpy())
         S.write_image(paths[2], rgba8_t.cpu().numpy())
