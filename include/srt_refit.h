@@ -12,9 +12,11 @@
  * vertices), so a refit at unchanged vertices reproduces the built boxes as values.
  *
  * Out of scope:
- *   - the path tracer's device scene: callers use srt_bvh_refit + srt_upload_scene;
  *   - rebuilds, topology changes and a changing n_verts;
  *   - motion of lights.
+ *
+ * The path tracer's own device scene follows the same rule through srt_scene_refit.h (srt_upload_scene_refit,
+ * then srt_scene_refit per frame), which replaces srt_bvh_refit + srt_upload_scene in a frame loop.
  *
  * Additive to srt_amd.h and srt_query.h (SRT_ABI_VERSION and SRT_QUERY_ABI_VERSION are unchanged); versioned
  * on its own.

@@ -5,14 +5,8 @@
 #include <string>
 #include <vector>
 
+#include "capi_objects.hpp"
 #include "srt_internal.hpp"
-
-struct srt_model {
-  std::unique_ptr<srt::Model> m;
-};
-struct srt_scene {
-  std::unique_ptr<srt::Scene> s;
-};
 
 extern "C" {
 

@@ -13,6 +13,8 @@
 
 #include <cstdint>
 
+#include "refit_fold.hpp"
+
 namespace srt {
 namespace refit {
 
@@ -27,34 +29,8 @@ struct RParams {
   uint32_t n_verts, n_tris, n_roots, tail_levels;
 };
 
-struct Box {
-  float lo[3], hi[3];
-};
-
-// Keeps a register's value out of the optimiser's sight, so that an access stays the 16 B it is written as: a
-// position's unused pad would narrow its gather to 12 B, and a record's unchanged .w its store.
-__device__ __forceinline__ float opaque(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-__device__ __forceinline__ float4 load_vert(const RParams& rp, uint32_t i) {
-  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (i < rp.n_verts) {
-    v = rp.verts[2 * (size_t)i];
-    v.w = opaque(v.w);
-  }
-  return v;
-}
-
-__device__ __forceinline__ void fold(Box& b, const float4& v) {
-  b.lo[0] = v.x < b.lo[0] ? v.x : b.lo[0];
-  b.lo[1] = v.y < b.lo[1] ? v.y : b.lo[1];
-  b.lo[2] = v.z < b.lo[2] ? v.z : b.lo[2];
-  b.hi[0] = v.x > b.hi[0] ? v.x : b.hi[0];
-  b.hi[1] = v.y > b.hi[1] ? v.y : b.hi[1];
-  b.hi[2] = v.z > b.hi[2] ? v.z : b.hi[2];
-}
+// (Box, opaque, fold and the position gather: refit_fold.hpp, shared with the path tracer's scene refit)
+__device__ __forceinline__ float4 load_vert(const RParams& rp, uint32_t i) { return load_pos(rp.verts, rp.n_verts, i); }
 
 // The box of one slot: (ref, cnt) are its .w fields, which stay.
 __device__ __forceinline__ Box slot_box(const RParams& rp, uint32_t ref, uint32_t cnt) {

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "scene_image_maps.hpp"
 #include "scene_layout.hpp"
 
 namespace srt {
@@ -71,6 +72,12 @@ ScenePolicy ChooseScenePolicy(uint32_t n_nodes, uint32_t n_tris, int treelet_dep
 void BuildSceneImage(const SceneArrays& in, int depth, std::vector<std::pair<uint32_t, uint32_t>> tri_ranges,
                      const std::vector<uint8_t>& reach, const ScenePolicy& policy, const BuildConsts& k,
                      size_t lights_at_upload, SceneImage* out) {
+  BuildSceneImageMaps(in, depth, std::move(tri_ranges), reach, policy, k, lights_at_upload, out, nullptr);
+}
+
+void BuildSceneImageMaps(const SceneArrays& in, int depth, std::vector<std::pair<uint32_t, uint32_t>> tri_ranges,
+                         const std::vector<uint8_t>& reach, const ScenePolicy& policy, const BuildConsts& k,
+                         size_t lights_at_upload, SceneImage* out, SceneMaps* maps) {
   const srt_bvh_node* nodes = in.nodes;
   const uint32_t n_nodes = in.n_nodes, n_tris = in.n_tris, n_mats = in.n_mats, n_verts = in.n_verts;
   SceneImage& img = *out;
@@ -250,6 +257,14 @@ void BuildSceneImage(const SceneArrays& in, int depth, std::vector<std::pair<uin
   // larger arrays than cooperative loads index (only reachable with SRT_GLOBAL_FUSED_MODE=1 past 600 MB)
   // take the IL instance
   img.fused = policy.fused && !(k.coop && !CoopIndexFits((uint64_t)n_slots + k.node_pad, n_tslots, k));
+  if (maps) {
+    if (!tris_laid) {
+      tslot.resize(n_tris);
+      for (uint32_t t = 0; t < n_tris; ++t) tslot[t] = t;
+    }
+    maps->node_slot = std::move(remap);
+    maps->tri_slot = std::move(tslot);
+  }
 }
 
 }  // namespace srt

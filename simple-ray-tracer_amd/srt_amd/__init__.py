@@ -383,6 +383,7 @@ class Compute:
         self.device = device
         self._stream = stream
         self._ctx = None
+        self._refit = None  # the srt_scene_refit object of bind_scene(scene, refit=True)
         self.program = 0
         self.width = 0
         self.height = 0
@@ -410,13 +411,20 @@ class Compute:
             self.Init()
         return self._ctx
 
+    def _drop_refit(self):
+        if getattr(self, "_refit", None) is not None and _lib._lib is not None:
+            _lib._lib.srt_scene_refit_destroy(self._refit)
+        self._refit = None
+
     def close(self):
+        self._drop_refit()
         if self._ctx is not None:
             lib().srt_destroy(self._ctx)
             self._ctx = None
 
     def __del__(self):
         try:
+            self._drop_refit()
             if self._ctx is not None and _lib._lib is not None:
                 _lib._lib.srt_destroy(self._ctx)
                 self._ctx = None
@@ -491,15 +499,66 @@ class Compute:
                                                       for t in keep])
         check(lib().srt_upload_textures(self.ctx, descs, len(keep)), "bind_textures")
 
-    def bind_scene(self, scene: Scene):
+    def bind_scene(self, scene: Scene, refit: bool = False):
+        """``UploadModelDataToGPU``.  ``refit=True`` (include/srt_scene_refit.h) uploads the same scene and keeps
+        the object that lets :meth:`refit` move it to new vertex positions on the device; it lives until the
+        next ``bind_scene``."""
         s = scene
+        self._drop_refit()  # the object of an earlier upload ends with that upload
         if s.sample_textures:
             self.bind_textures(s.textures)
         tex = None if s.sample_textures else np.ascontiguousarray(s.tex_albedo, np.float32)
-        check(lib().srt_upload_scene(self.ctx, _ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes),
-                                     _ptr(s.mats), _ptr(tex), len(s.mats), _ptr(s.tris), len(s.tris), _ptr(s.verts),
-                                     len(s.verts)),
-              "UploadModelDataToGPU")
+        args = (self.ctx, _ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.mats), _ptr(tex), len(s.mats),
+                _ptr(s.tris), len(s.tris), _ptr(s.verts), len(s.verts))
+        if not refit:
+            check(lib().srt_upload_scene(*args), "UploadModelDataToGPU")
+            return
+        h = C.c_void_p()
+        check(lib().srt_upload_scene_refit(*args, C.byref(h)), "srt_upload_scene_refit")
+        self._refit = h
+
+    def refit(self, verts, read_roots: bool = False):
+        """Refit the device scene of ``bind_scene(scene, refit=True)`` to new vertices (``srt_scene_refit``): a
+        contiguous float32 ``[n_verts, 8]`` tensor of ``srt_vertex`` records on the context's device -- only
+        enqueued on the context's stream, which is made to wait for ``torch.cuda.current_stream()`` first -- or a
+        numpy ``VERT_DTYPE`` array, which is uploaded first and synchronises.  ``read_roots=True``
+        (``SRT_SCENE_REFIT_READ_ROOTS``) synchronises, reads the root boxes back and keeps tile culling on."""
+        import torch
+
+        from ._stage import verts_arg
+        if self._refit is None:
+            raise RuntimeError("Compute.refit needs bind_scene(scene, refit=True)")
+        if isinstance(verts, np.ndarray):
+            host = np.ascontiguousarray(verts, dtype=VERT_DTYPE).view(np.float32).reshape(-1, 8)
+            self.refit(torch.from_numpy(host).to(f"cuda:{self.device}"), read_roots)
+            self.Finish()  # the upload may go once the kernels have read it
+            return
+        ptr, _ = verts_arg(verts, self.device)
+        ext = torch.cuda.ExternalStream(int(lib().srt_stream(self.ctx) or 0), device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        ext.wait_stream(cur)  # the vertices are ready where the kernels run ...
+        check(lib().srt_scene_refit(self._refit, C.c_void_p(ptr), verts.shape[0],
+                                    _lib.SRT_SCENE_REFIT_READ_ROOTS if read_roots else 0), "srt_scene_refit")
+        cur.wait_stream(ext)  # ... and are not reused on the caller's stream before they have been read
+
+    def refit_get_int(self, name: str) -> int:
+        """``srt_scene_refit_get_int``: "refit.launches", "refit.heights", "refit.count", "refit.bytes",
+        "refit.treelets"."""
+        if self._refit is None:
+            raise RuntimeError("Compute.refit_get_int needs bind_scene(scene, refit=True)")
+        v = C.c_int()
+        check(lib().srt_scene_refit_get_int(self._refit, name.encode(), C.byref(v)), f"srt_scene_refit_get_int({name})")
+        return v.value
+
+    def scene_device(self):
+        """The device scene ``(nodes, nodes_t, tris)`` as uint32 ``[n, 4]`` numpy arrays, one 16-B value a row;
+        ``nodes_t`` is None without a treelet copy (``srt_scene_copy_device``: a test and debug readback;
+        synchronises)."""
+        sizes = (C.c_size_t * 3)()
+        check(lib().srt_scene_device_bytes(self.ctx, sizes), "srt_scene_device_bytes")
+        out = [np.zeros((int(b) // 16, 4), np.uint32) if b else None for b in sizes]
+        check(lib().srt_scene_copy_device(self.ctx, *[_ptr(a) for a in out]), "srt_scene_copy_device")
+        return tuple(out)
 
     def set_tiling(self, rank: int, nranks: int, band_rows: int = 16):
         check(lib().srt_set_tiling(self.ctx, rank, nranks, band_rows), "set_tiling")

@@ -339,6 +339,21 @@ _SURFACE_REFIT_SIGS = {
 }
 SURFACE_REFIT_SYMBOLS = tuple(_SURFACE_REFIT_SIGS)
 
+SRT_SCENE_REFIT_READ_ROOTS = 1
+# include/srt_scene_refit.h: the refit of the path tracer's own device scene (its own header and version)
+_SCENE_REFIT_SIGS = {
+    "srt_scene_refit_abi_version": (C.c_int, []),
+    "srt_upload_scene_refit": (C.c_int, [P, P, C.c_uint32, P, C.c_uint32, P, P, C.c_uint32, P, C.c_uint32, P,
+                                         C.c_uint32, C.POINTER(P)]),
+    "srt_upload_scene_obj_refit": (C.c_int, [P, P, C.POINTER(P)]),
+    "srt_scene_refit_destroy": (C.c_int, [P]),
+    "srt_scene_refit": (C.c_int, [P, P, C.c_uint32, C.c_uint32]),
+    "srt_scene_refit_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_scene_copy_device": (C.c_int, [P, P, P, P]),
+    "srt_scene_device_bytes": (C.c_int, [P, C.POINTER(C.c_size_t)]),
+}
+SCENE_REFIT_SYMBOLS = tuple(_SCENE_REFIT_SIGS)
+
 _lib = None
 
 
@@ -373,7 +388,8 @@ def lib() -> C.CDLL:
         for name, (res, args) in (list(_QUERY_SIGS.items()) + list(_DENOISE_SIGS.items()) + list(_TEMPORAL_SIGS.items())
                                   + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
                                   + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
-                                  + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())):
+                                  + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
+                                  + list(_SCENE_REFIT_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -51,7 +51,8 @@ def main():
                          "--denoise the guide query is refit on the device (Query(scene, refit=True).refit), as is "
                          "the surface object of --albedo (Surface(scene, refit=True).refit).  With --orbit K the camera "
                          "stands still and the wave's phase advances by WAVE_PHASE_STEP per frame: each frame's vertices "
-                         "go to the renderer (host refit), the query, the temporal object, whose history follows the "
+                         "go to the renderer (bound once with refit=True, then Compute.refit on the device: "
+                         "include/srt_scene_refit.h), the query, the temporal object, whose history follows the "
                          "surface (include/srt_temporal_deform.h), and with --albedo the surface object")
     a = ap.parse_args()
     if a.wave and a.scene == "spheres":
@@ -180,8 +181,9 @@ def spin_frame(scene, degrees):
 def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False):
     """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
     (degrees per frame) under a still camera while the first model turns, or with `wave` (the amplitude) under a
-    still camera while the wave's phase advances -- the per-frame calls of a deforming mesh: the host refit and
-    bind_scene for the renderer, Query.refit, Temporal.set_vertices and, with `albedo`, Surface.refit, whose attrs
+    still camera while the wave's phase advances -- the per-frame calls of a deforming mesh, all on the device
+    vertices: Compute.refit for the renderer (bound once with refit=True; no per-frame bind_scene), Query.refit,
+    Temporal.set_vertices and, with `albedo`, Surface.refit, whose attrs
     then demodulate the two filtered images.  Every frame goes through
     srt_amd.temporal.Temporal (guide: a closest-hit query of the pixel-centre rays).  Writes the last frame raw,
     denoised, and temporally accumulated then denoised, and with `variance` also temporally accumulated then through
@@ -207,6 +209,7 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo
         q.set_bvh_count(setup.bvh_count)
         if wave:
             tp.set_mesh(setup.scene)
+            c.bind_scene(setup.scene, refit=True)  # once: the frames refit it on the device (srt_scene_refit.h)
         if albedo:
             surf.set_bvh_count(setup.bvh_count)
         if variance:
@@ -220,8 +223,8 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo
                 tp.set_models([frame])
             elif wave:  # the per-frame calls of a deforming mesh
                 verts = R.wave_vertices(setup.scene.verts, wave, WAVE_PHASE_STEP * k)
-                c.bind_scene(S.refit_scene(setup.scene, verts))
                 vdev = torch.from_numpy(np.ascontiguousarray(verts).view(np.float32).reshape(-1, 8)).to(f"cuda:{r.compute.device}")
+                c.refit(vdev)
                 q.refit(vdev)
                 tp.set_vertices(vdev)
                 if albedo:
