@@ -1,6 +1,6 @@
-// srt/query.hpp -- header-only C++ mirror of include/srt_query.h and include/srt_refit.h: srt::Query, RAII over
-// the C ABI with the same method names, and AssetUtils::RefitBVH.  Errors throw std::runtime_error carrying
-// srt_last_error().
+// srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h and include/srt_rebuild.h:
+// srt::Query, RAII over the C ABI with the same method names, AssetUtils::RefitBVH and AssetUtils::BuildLBVH.
+// Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
 #include <cstdint>
@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "../srt_query.h"
+#include "../srt_rebuild.h"
 #include "../srt_refit.h"
 
 namespace srt {
@@ -46,6 +47,10 @@ class Query {
   }
   // srt_query_refit: `verts_dev` is a device array of `n` srt_vertex records; only enqueues on the query's stream.
   void Refit(const srt_vertex* verts_dev, uint32_t n) { Check(srt_query_refit(q_, verts_dev, n), "srt_query_refit"); }
+  // include/srt_rebuild.h, for an object created with SRT_QUERY_REFIT over one model: EnableRebuild allocates, Rebuild
+  // builds a linear BVH over the triangles at `verts_dev` on the device (it synchronises the stream once).
+  void EnableRebuild() { Check(srt_query_enable_rebuild(q_), "srt_query_enable_rebuild"); }
+  void Rebuild(const srt_vertex* verts_dev, uint32_t n) { Check(srt_query_rebuild(q_, verts_dev, n), "srt_query_rebuild"); }
   // Device pointers; both only enqueue on the query's stream.
   void closest(const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
     Check(srt_query_closest(q_, rays_dev, n, hits_dev), "srt_query_closest");
@@ -76,6 +81,14 @@ inline void RefitBVH(const srt_bvh_record* bvhs, uint32_t n_bvhs, srt_bvh_node* 
                      const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts) {
   if (int rc = srt_bvh_refit(bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts))
     throw std::runtime_error("srt_bvh_refit failed with status " + std::to_string(rc) + ": " + srt_last_error());
+}
+
+// srt_bvh_build_lbvh: the host mirror of Query::Rebuild -- 2 * n_tris - 1 nodes (root node 0), the triangles in the
+// tree's order and position -> input index.
+inline void BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts,
+                      srt_bvh_node* nodes_out, srt_triangle* tris_out, uint32_t* order_out) {
+  if (int rc = srt_bvh_build_lbvh(tris, n_tris, verts, n_verts, nodes_out, tris_out, order_out))
+    throw std::runtime_error("srt_bvh_build_lbvh failed with status " + std::to_string(rc) + ": " + srt_last_error());
 }
 
 }  // namespace AssetUtils

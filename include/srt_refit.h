@@ -12,7 +12,7 @@
  * vertices), so a refit at unchanged vertices reproduces the built boxes as values.
  *
  * Out of scope:
- *   - rebuilds, topology changes and a changing n_verts;
+ *   - a new topology (srt_rebuild.h builds one on the device for a query object) and a changing n_verts;
  *   - motion of lights.
  *
  * The path tracer's own device scene follows the same rule through srt_scene_refit.h (srt_upload_scene_refit,

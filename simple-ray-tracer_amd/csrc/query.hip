@@ -58,20 +58,10 @@ int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bv
   q->pairs_bytes = pb;
   q->roots_bytes = rb;
   q->tris_bytes = tb;
-  // persistent grid: the blocks the device holds at once
   hipDeviceProp_t prop;
   STAGE_HIP_OK(hipGetDeviceProperties(&prop, q->device));
-  for (int any = 0; any < 2; ++any) {
-    const void* fn = any ? Instance<true>(q->plan.in_hbm, q->plan.packed) : Instance<false>(q->plan.in_hbm, q->plan.packed);
-    if (q->plan.lds_bytes > 48 * 1024)
-      STAGE_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
-    int per_cu = 0;
-    STAGE_HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
-    per_cu = std::max(1, std::min(per_cu, LdsBlocksPerCu(q->plan.lds_bytes)));
-    if (q->plan.in_hbm) per_cu = std::min(per_cu, 4);  // each block holds an HBM stack area
-    q->max_blocks[any] = per_cu * std::max(1, prop.multiProcessorCount);
-  }
-  return SRT_OK;
+  q->cu_count = prop.multiProcessorCount;
+  return srt::query::PlanGrid(q);
 }
 
 template <bool ANY>
@@ -123,6 +113,27 @@ int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
 
 }  // namespace
 
+namespace srt {
+namespace query {
+
+// persistent grid: the blocks the device holds at once
+int PlanGrid(srt_query* q) {
+  for (int any = 0; any < 2; ++any) {
+    const void* fn = any ? Instance<true>(q->plan.in_hbm, q->plan.packed) : Instance<false>(q->plan.in_hbm, q->plan.packed);
+    if (q->plan.lds_bytes > 48 * 1024)
+      STAGE_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
+    int per_cu = 0;
+    STAGE_HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
+    per_cu = std::max(1, std::min(per_cu, LdsBlocksPerCu(q->plan.lds_bytes)));
+    if (q->plan.in_hbm) per_cu = std::min(per_cu, 4);  // each block holds an HBM stack area
+    q->max_blocks[any] = per_cu * std::max(1, q->cu_count);
+  }
+  return SRT_OK;
+}
+
+}  // namespace query
+}  // namespace srt
+
 extern "C" {
 
 int srt_query_abi_version(void) { return SRT_QUERY_ABI_VERSION; }
@@ -155,6 +166,7 @@ int srt_query_create_ex(int device, void* stream, const srt_bvh_record* bvhs, ui
   }
   srt::stage::Owned<srt_query> q(new srt_query());
   q->n_bvhs = q->bvh_count = n_bvhs;
+  q->first_index0 = bvhs[0].first_index;
   q->plan = srt::query::PlanStack(lay, n_tris);
   // Refill threshold ("Ray queries"): a scene the caches hold (Rubik, 74 KB) gains from
   // refilling early (surface rays 1.90 ms with 1, 1.54 with 40-56, 1.59 with 64); the 262k-triangle knot
@@ -211,7 +223,10 @@ int srt_query_update_model_matrix(srt_query* q, uint32_t index, const float fram
 }
 
 int srt_query_closest(srt_query* q, const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
-  return Launch<false>(q, rays_dev, n, hits_dev);
+  if (int rc = Launch<false>(q, rays_dev, n, hits_dev)) return rc;
+  // a rebuilt object holds its triangle records in the LBVH's order (include/srt_rebuild.h)
+  if (n && q->rebuild && q->rebuild->count > 0) return srt::rebuild::EnqueueRemap(q, hits_dev, n);
+  return SRT_OK;
 }
 
 int srt_query_occluded(srt_query* q, const srt_ray* rays_dev, uint32_t n, uint8_t* occluded_dev) {
@@ -238,6 +253,11 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   else if (n == "layout.pairs") *v = srt::stage::SaturateInt(q->pairs_bytes);
   else if (n == "layout.roots") *v = srt::stage::SaturateInt(q->roots_bytes);
   else if (n == "layout.tris") *v = srt::stage::SaturateInt(q->tris_bytes);
+  else if (n == "rebuild") *v = q->rebuild ? 1 : 0;
+  else if (n == "rebuild.count") *v = q->rebuild ? q->rebuild->count : 0;
+  else if (n == "rebuild.bytes") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->bytes) : 0;
+  else if (n == "rebuild.launches") *v = q->rebuild ? q->rebuild->launches : 0;
+  else if (n == "rebuild.depth") *v = q->rebuild ? q->rebuild->depth : 0;
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }

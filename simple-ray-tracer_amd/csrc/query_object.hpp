@@ -4,11 +4,40 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
+#include <vector>
 
 #include "../../include/srt_refit.h"
 #include "query_host.hpp"
+#include "rebuild_host.hpp"
 #include "refit_host.hpp"
 #include "stage.hpp"
+
+namespace srt {
+namespace rebuild {
+
+// What srt_query_enable_rebuild adds to an object (rebuild.hip, include/srt_rebuild.h).  Until the first rebuild
+// d_pairs / d_triples / d_schedule are the LBVH's arrays-to-be; that rebuild exchanges them with the object's,
+// and they then hold the creation-order index triples (kept: every rebuild sorts from them) and the replaced
+// tree's pairs and schedule (freed after that rebuild's synchronisation).
+struct State {
+  stage::DevPtr<float4> d_pairs;
+  stage::DevPtr<uint4> d_triples;
+  stage::DevPtr<uint32_t> d_schedule;
+  stage::DevPtr<uint32_t> d_keys_in, d_vals_in, d_keys, d_order;  // the sort's input and output
+  stage::DevPtr<uint8_t> d_temp;                                  // its temporary storage
+  size_t temp_bytes = 0;
+  stage::DevPtr<uint32_t> d_parent, d_height;
+  stage::DevPtr<uint32_t> d_zeroed;  // zeroed by every rebuild: counts, cursor, then the arrival words
+  stage::DevPtr<float> d_box;        // the scene box, then the partial boxes
+  size_t bytes = 0;
+  int count = 0, launches = 0, depth = 0;
+  uint32_t summary[kSummaryInts] = {};
+  std::vector<uint32_t> tail_first;  // host copy of the tail's level offsets while their upload is in flight
+};
+
+}  // namespace rebuild
+}  // namespace srt
 
 struct srt_query : srt::stage::Stage {
   srt::stage::DevPtr<float4> d_pairs, d_roots, d_tris;
@@ -31,13 +60,35 @@ struct srt_query : srt::stage::Stage {
   uint32_t n_pairs = 0, n_tris = 0, n_verts = 0;
   size_t refit_bytes = 0;
   int refit_count = 0;
+  // srt_query_enable_rebuild only (rebuild.hip); null otherwise
+  uint32_t first_index0 = 0;  // of BVH record 0
+  int cu_count = 0;
+  std::unique_ptr<srt::rebuild::State> rebuild;
 };
 
 namespace srt {
+namespace query {
+
+// The persistent grids of the two kernel instances q->plan selects (query.hip; at creation, and again when a
+// rebuild changes the plan).
+int PlanGrid(srt_query* q);
+
+}  // namespace query
+
 namespace refit {
 
 // Uploads the refit data of a query object created with SRT_QUERY_REFIT (on q->stream; synchronises).
 int Attach(srt_query* q, const query::Layout& lay, const srt_triangle* tris, uint32_t n_tris, uint32_t n_verts);
 
+// srt_query_refit after its argument checks: the launches, on q->stream.
+int Enqueue(srt_query* q, const srt_vertex* verts_dev);
+
 }  // namespace refit
+
+namespace rebuild {
+
+// The launch srt_query_closest adds on a rebuilt object: hits_dev[i].triangle, a position, becomes the creation index.
+int EnqueueRemap(srt_query* q, srt_hit* hits_dev, uint32_t n);
+
+}  // namespace rebuild
 }  // namespace srt

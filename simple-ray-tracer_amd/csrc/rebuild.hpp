@@ -1,0 +1,263 @@
+// rebuild.hpp -- the kernels of the device rebuild (include/srt_rebuild.h) over query_host.hpp's layout.  The
+// sort between keys_kernel and karras_kernel is hipcub's, and the boxes and triangle records are refit.hpp's
+// kernels over the schedule made here.
+//
+// box_partial_kernel / box_final_kernel: the scene box, a two-stage min / max reduction over the triangles.
+// keys_kernel: one lane per triangle in creation order; its Morton key and its own index as the sort's value.
+// karras_kernel: one lane per internal node; the .w fields of its pair's four records (the boxes are the
+//   refit's), the parents of its two children, and the roots' .w.
+// permute_kernel: one lane per position; the 16-B index triple of the triangle sorted there.
+// climb_kernel: one lane per leaf climbs towards the root.  At a node it exchanges its side's value into the
+//   node's arrival word: the first arriver reads 0 back and stops, the second reads the other side's value --
+//   the word itself carries what is handed over, nothing else written in this launch is read in it -- computes
+//   the pair's height and goes on.  No lane waits, spins or polls on another; the climb is bounded by the depth.
+// schedule_kernel: a counting sort of the pairs by height into the format refit.hpp reads (the order inside a
+//   height is free); a block takes its share of each height with one atomic per height.
+// remap_kernel: one lane per hit; the position srt_query_closest reported becomes the creation index.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "rebuild_rule.hpp"
+#include "refit_fold.hpp"
+
+namespace srt {
+namespace rebuild {
+
+constexpr uint32_t kBlock = 256;
+constexpr uint32_t kBoxBlocks = 256;  // most partial boxes of the first stage (the second is one block)
+constexpr uint32_t kMissTri = 0xFFFFFFFFu;
+
+struct BParams {
+  float4* pairs;            // 4 float4 per sibling pair (n_tris - 1 of them)
+  float4* roots;            // 2 float4 per root record, two records
+  const uint4* triples0;    // creation order: v0, v1, v2, material
+  uint4* triples;           // sorted order
+  const float4* verts;      // 2 float4 per srt_vertex
+  float* box_partial;       // 8 floats per block of the first stage: lo xyz, -, hi xyz, -
+  float* box;               // 8 floats
+  uint32_t* keys_in;        // creation order
+  uint32_t* vals_in;
+  const uint32_t* keys;     // sorted
+  const uint32_t* order;    // sorted: position -> creation index
+  uint32_t* parent;         // [0, n - 1): of internal nodes; [n - 1, 2n - 1): of leaf positions
+  uint32_t* arrive;         // n - 1 arrival words, zero at launch
+  uint32_t* height;         // n - 1
+  uint32_t* counts;         // kHeightBins pairs per height, zero at launch
+  uint32_t* cursor;         // kHeightBins, zero at launch
+  uint32_t* schedule;       // n - 1 pair indices by height
+  uint32_t n_verts, n_tris, box_blocks;
+};
+
+struct Span3 {
+  float lo[3], hi[3];
+};
+
+// min / max over the triangle's three vertices (values only: rule 1).
+__device__ __forceinline__ Span3 tri_span(const BParams& bp, uint32_t t) {
+  const uint4 idx = bp.triples0[t];
+  const float4 a = refit::load_pos(bp.verts, bp.n_verts, idx.x), b = refit::load_pos(bp.verts, bp.n_verts, idx.y),
+               c = refit::load_pos(bp.verts, bp.n_verts, idx.z);
+  refit::Box box;
+  box.lo[0] = box.hi[0] = a.x;
+  box.lo[1] = box.hi[1] = a.y;
+  box.lo[2] = box.hi[2] = a.z;
+  refit::fold(box, b);
+  refit::fold(box, c);
+  Span3 s;
+  for (int k = 0; k < 3; ++k) {
+    s.lo[k] = box.lo[k];
+    s.hi[k] = box.hi[k];
+  }
+  return s;
+}
+
+__device__ __forceinline__ void span_merge(Span3& s, const Span3& o) {
+  for (int k = 0; k < 3; ++k) {
+    s.lo[k] = o.lo[k] < s.lo[k] ? o.lo[k] : s.lo[k];
+    s.hi[k] = o.hi[k] > s.hi[k] ? o.hi[k] : s.hi[k];
+  }
+}
+
+// The block's merged span in every lane of wave 0 (all 256 lanes call it; `have`: the lane holds a span).
+__device__ __forceinline__ Span3 block_span(Span3 s, bool have, const Span3& neutral) {
+  __shared__ float sh[kBlock / 64][6];
+  if (!have) s = neutral;
+  for (int off = 32; off > 0; off >>= 1) {
+    Span3 o;
+    for (int k = 0; k < 3; ++k) {
+      o.lo[k] = __shfl_xor(s.lo[k], off, 64);
+      o.hi[k] = __shfl_xor(s.hi[k], off, 64);
+    }
+    span_merge(s, o);
+  }
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0u)
+    for (int k = 0; k < 3; ++k) {
+      sh[wave][k] = s.lo[k];
+      sh[wave][3 + k] = s.hi[k];
+    }
+  __syncthreads();
+  for (int k = 0; k < 3; ++k) {
+    s.lo[k] = sh[0][k];
+    s.hi[k] = sh[0][3 + k];
+  }
+  for (uint32_t w = 1; w < kBlock / 64; ++w) {
+    Span3 o;
+    for (int k = 0; k < 3; ++k) {
+      o.lo[k] = sh[w][k];
+      o.hi[k] = sh[w][3 + k];
+    }
+    span_merge(s, o);
+  }
+  return s;
+}
+
+// Stage 1: block b folds triangles b * 256 + lane, + box_blocks * 256, ...; triangle 0's span is the neutral
+// element (it is part of the result anyway), so no infinity enters.
+__global__ __launch_bounds__(256) void box_partial_kernel(BParams bp) {
+  const Span3 neutral = tri_span(bp, 0);
+  Span3 s = neutral;
+  for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < bp.n_tris; t += (uint64_t)bp.box_blocks * kBlock)
+    span_merge(s, tri_span(bp, (uint32_t)t));
+  s = block_span(s, true, neutral);
+  if (threadIdx.x == 0) {
+    float* o = bp.box_partial + 8 * (size_t)blockIdx.x;
+    for (int k = 0; k < 3; ++k) {
+      o[k] = s.lo[k];
+      o[4 + k] = s.hi[k];
+    }
+  }
+}
+
+// Stage 2: one block over the box_blocks <= 256 partial boxes.
+__global__ __launch_bounds__(256) void box_final_kernel(BParams bp) {
+  Span3 neutral;
+  for (int k = 0; k < 3; ++k) {
+    neutral.lo[k] = bp.box_partial[k];
+    neutral.hi[k] = bp.box_partial[4 + k];
+  }
+  Span3 s = neutral;
+  const bool have = threadIdx.x < bp.box_blocks;
+  if (have) {
+    const float* p = bp.box_partial + 8 * (size_t)threadIdx.x;
+    for (int k = 0; k < 3; ++k) {
+      s.lo[k] = p[k];
+      s.hi[k] = p[4 + k];
+    }
+  }
+  s = block_span(s, have, neutral);
+  if (threadIdx.x == 0)
+    for (int k = 0; k < 3; ++k) {
+      bp.box[k] = s.lo[k];
+      bp.box[4 + k] = s.hi[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void keys_kernel(BParams bp) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= bp.n_tris) return;
+  const Span3 s = tri_span(bp, t);
+  uint32_t q[3];
+  for (int k = 0; k < 3; ++k) q[k] = Cell(bp.box[k], bp.box[4 + k], s.lo[k], s.hi[k]);
+  bp.keys_in[t] = Morton(q[0], q[1], q[2]);
+  bp.vals_in[t] = t;
+}
+
+// One record's .w fields; the bounds are the refit's to write.
+__device__ __forceinline__ void put_child(float4* rec, const Child& c) {
+  rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c.index));
+  rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c.leaf ? 1u : 0u));
+}
+
+__global__ __launch_bounds__(256) void karras_kernel(BParams bp) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;  // >= 2
+  if (i == 0) {  // both root records (the BVH record and the ghost root) reference pair 0
+    const Child root{0u, false};
+    put_child(bp.roots, root);
+    put_child(bp.roots + 2, root);
+  }
+  if (i + 1 >= n) return;
+  Child l, r;
+  KarrasNode(bp.keys, n, i, &l, &r);
+  float4* rec = bp.pairs + 4 * (size_t)i;
+  put_child(rec, l);
+  put_child(rec + 2, r);
+  // a child index is < n - 1 (internal) or < n (leaf) by construction; the clamp keeps a store inside the array
+  const uint32_t li = l.leaf ? n - 1 + (l.index < n ? l.index : n - 1) : (l.index < n - 1 ? l.index : n - 2);
+  const uint32_t ri = r.leaf ? n - 1 + (r.index < n ? r.index : n - 1) : (r.index < n - 1 ? r.index : n - 2);
+  bp.parent[li] = i;
+  bp.parent[ri] = i;
+}
+
+__global__ __launch_bounds__(256) void permute_kernel(BParams bp) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= bp.n_tris) return;
+  const uint32_t src = bp.order[p];
+  bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];  // (a whole record: one 16-B load, one 16-B store)
+}
+
+__global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
+  __shared__ uint32_t bins[kHeightBins];
+  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t n = bp.n_tris;  // >= 2
+  const uint32_t leaf = blockIdx.x * kBlock + threadIdx.x;
+  if (leaf < n) {
+    uint32_t p = bp.parent[n - 1 + leaf];
+    uint32_t val = 0u;  // of a child: 0 for a leaf, its pair's height + 1 for an internal node
+    for (int step = 0; step < kHeightBins && p < n - 1; ++step) {
+      const uint32_t old = __hip_atomic_exchange(bp.arrive + p, val + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old == 0u) break;  // the first to arrive: the other side's lane carries on from here
+      uint32_t h = old - 1u > val ? old - 1u : val;
+      h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;  // (the depth bound keeps it below)
+      bp.height[p] = h;
+      atomicAdd(&bins[h], 1u);
+      if (p == 0u) break;  // the root
+      val = h + 1u;
+      p = bp.parent[p];
+    }
+  }
+  __syncthreads();  // (every lane arrives: the climb above waits for nothing)
+  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) atomicAdd(bp.counts + threadIdx.x, bins[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
+  __shared__ uint32_t bins[kHeightBins], base[kHeightBins];
+  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t n_pairs = bp.n_tris - 1u;
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t h = 0u, rank = 0u;
+  if (p < n_pairs) {
+    h = bp.height[p];
+    h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;
+    rank = atomicAdd(&bins[h], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) {
+    uint32_t first = 0u;  // of this height: the pairs of the heights under it
+    for (uint32_t k = 0; k < threadIdx.x; ++k) first += bp.counts[k];
+    base[threadIdx.x] = first + atomicAdd(bp.cursor + threadIdx.x, bins[threadIdx.x]);
+  }
+  __syncthreads();
+  if (p < n_pairs) {
+    const uint32_t at = base[h] + rank;
+    if (at < n_pairs) bp.schedule[at] = p;
+  }
+}
+
+// hits: 2 uint4 per srt_hit; the first dword is the triangle.
+__global__ __launch_bounds__(256) void remap_kernel(uint32_t* hits, const uint32_t* order, uint32_t n, uint32_t n_tris) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  uint32_t* tri = hits + 8 * (size_t)i;
+  const uint32_t pos = *tri;
+  if (pos != kMissTri && pos < n_tris) *tri = order[pos];
+}
+
+}  // namespace rebuild
+}  // namespace srt

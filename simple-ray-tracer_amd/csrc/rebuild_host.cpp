@@ -1,0 +1,139 @@
+// rebuild_host.cpp -- see rebuild_host.hpp.
+#include "rebuild_host.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+
+namespace srt {
+namespace rebuild {
+
+namespace {
+
+int Fail(std::string* err, const char* msg, int rc = SRT_ERR_INVALID) {
+  if (err) *err = msg;
+  return rc;
+}
+
+float Vert(const srt_vertex* verts, uint32_t n_verts, uint32_t i, int k) { return i < n_verts ? verts[i].vertex[k] : 0.0f; }
+
+// min / max over a triangle's three vertices, one component; only the values matter (rule 1)
+void Span(const srt_triangle& t, const srt_vertex* verts, uint32_t n_verts, int k, float* mn, float* mx) {
+  const float a = Vert(verts, n_verts, t.v0_idx, k), b = Vert(verts, n_verts, t.v1_idx, k), c = Vert(verts, n_verts, t.v2_idx, k);
+  *mn = refit::FoldMin(refit::FoldMin(a, b), c);
+  *mx = refit::FoldMax(refit::FoldMax(a, b), c);
+}
+
+}  // namespace
+
+void SceneBox(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, float lo[3], float hi[3]) {
+  for (int k = 0; k < 3; ++k) {
+    Span(tris[0], verts, n_verts, k, &lo[k], &hi[k]);
+    for (uint32_t t = 1; t < n_tris; ++t) {
+      float mn, mx;
+      Span(tris[t], verts, n_verts, k, &mn, &mx);
+      lo[k] = refit::FoldMin(lo[k], mn);
+      hi[k] = refit::FoldMax(hi[k], mx);
+    }
+  }
+}
+
+void Keys(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t* keys) {
+  float lo[3], hi[3];
+  SceneBox(tris, n_tris, verts, n_verts, lo, hi);
+  for (uint32_t t = 0; t < n_tris; ++t) {
+    uint32_t q[3];
+    for (int k = 0; k < 3; ++k) {
+      float mn, mx;
+      Span(tris[t], verts, n_verts, k, &mn, &mx);
+      q[k] = Cell(lo[k], hi[k], mn, mx);
+    }
+    keys[t] = Morton(q[0], q[1], q[2]);
+  }
+}
+
+int DepthBound(uint32_t n_tris) {
+  int log2 = 0;
+  while (log2 < 32 && (1ull << log2) < n_tris) ++log2;
+  return 30 + log2;
+}
+
+int BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, srt_bvh_node* nodes_out,
+              srt_triangle* tris_out, uint32_t* order_out, std::string* err) {
+  if (!tris || !nodes_out || !tris_out || !order_out || (n_verts && !verts)) return Fail(err, "null argument");
+  if (n_tris == 0) return Fail(err, "srt_bvh_build_lbvh: a tree needs at least one triangle");
+  if (n_tris >= kMaxTris) return Fail(err, "srt_bvh_build_lbvh: 2^30 triangles or more", SRT_ERR_LIMIT);
+  for (uint32_t i = 0; i < n_verts; ++i)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(verts[i].vertex[k])) return Fail(err, "srt_bvh_build_lbvh: a vertex position is not finite");
+  // rules 1-3: keys in input order, then a stable sort of the input indices
+  std::vector<uint32_t> keys(n_tris), order(n_tris);
+  Keys(tris, n_tris, verts, n_verts, keys.data());
+  std::iota(order.begin(), order.end(), 0u);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+  std::vector<uint32_t> sorted(n_tris);
+  for (uint32_t p = 0; p < n_tris; ++p) {
+    sorted[p] = keys[order[p]];
+    tris_out[p] = tris[order[p]];
+    order_out[p] = order[p];
+  }
+  // rule 4: the children of internal node i are nodes 2i + 1 and 2i + 2; node 0 is the root
+  const size_t n_nodes = 2 * (size_t)n_tris - 1;
+  for (size_t i = 0; i < n_nodes; ++i) nodes_out[i] = srt_bvh_node{};
+  auto put = [&](size_t at, const Child& c) {
+    nodes_out[at].first_child_or_prim_index = c.leaf ? c.index : 2 * c.index + 1;
+    nodes_out[at].prim_count = c.leaf ? 1u : 0u;
+  };
+  if (n_tris == 1) {
+    put(0, Child{0, true});
+  } else {
+    put(0, Child{0, false});
+    for (uint32_t i = 0; i + 1 < n_tris; ++i) {
+      Child l, r;
+      KarrasNode(sorted.data(), n_tris, i, &l, &r);
+      put(2 * (size_t)i + 1, l);
+      put(2 * (size_t)i + 2, r);
+    }
+  }
+  // rule 5: srt_refit.h's fold on the new topology (which also walks the tree: a malformed one fails here)
+  srt_bvh_record rec{};
+  return refit::RefitNodes(&rec, 1, nodes_out, (uint32_t)n_nodes, tris_out, n_tris, verts, n_verts, err);
+}
+
+int CheckEnable(bool have_object, bool refit, uint32_t n_bvhs, uint32_t first_index, uint32_t n_tris, std::string* err) {
+  if (!have_object) return Fail(err, "srt_query_enable_rebuild: null object");
+  if (!refit) return Fail(err, "srt_query_enable_rebuild: the object was created without SRT_QUERY_REFIT");
+  if (n_bvhs != 1) return Fail(err, "srt_query_enable_rebuild: the scene has more than one BVH record (one model is the scope)");
+  if (first_index != 0) return Fail(err, "srt_query_enable_rebuild: the BVH record's first_index is not 0");
+  if (n_tris >= kMaxTris) return Fail(err, "srt_query_enable_rebuild: 2^30 triangles or more", SRT_ERR_LIMIT);
+  return SRT_OK;
+}
+
+int CheckRebuild(bool have_object, bool refit, bool enabled, const void* verts_dev, uint32_t n_verts, uint32_t want_verts,
+                 std::string* err) {
+  if (!have_object) return Fail(err, "srt_query_rebuild: null object");
+  if (!refit) return Fail(err, "srt_query_rebuild: the object was created without SRT_QUERY_REFIT");
+  if (!enabled) return Fail(err, "srt_query_rebuild: rebuild is not enabled (srt_query_enable_rebuild)");
+  if (!verts_dev || (reinterpret_cast<uintptr_t>(verts_dev) & 15u))
+    return Fail(err, "srt_query_rebuild: verts_dev must be a 16-byte aligned device pointer");
+  if (n_verts != want_verts) return Fail(err, "srt_query_rebuild: n_verts differs from the count at creation");
+  return SRT_OK;
+}
+
+bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out) {
+  refit::Schedule s;
+  while (s.heights < (uint32_t)n_counts && counts[s.heights] > 0) ++s.heights;
+  uint64_t total = 0;
+  for (int h = 0; h < n_counts; ++h) total += counts[h];
+  s.first.assign((size_t)s.heights + 1, 0);
+  for (uint32_t h = 0; h < s.heights; ++h) s.first[h + 1] = s.first[h] + counts[h];
+  if (total != n_pairs || s.first[s.heights] != n_pairs) return false;  // a gap, or pairs that never arrived
+  s.tail_begin = s.heights;
+  while (s.tail_begin > 0 && s.first[s.tail_begin] - s.first[s.tail_begin - 1] <= refit::kBlock) --s.tail_begin;
+  s.launches = 1 + s.tail_begin + 1;
+  *out = std::move(s);
+  return true;
+}
+
+}  // namespace rebuild
+}  // namespace srt

@@ -1,0 +1,43 @@
+// rebuild_host.hpp -- host-only parts of the device rebuild (include/srt_rebuild.h): the host mirror of the LBVH
+// (srt_bvh_build_lbvh), the argument contract of the two object calls, and the refit schedule and depth from the
+// pair counts per height the device reports.  No device, no HIP header: tests/cpp/test_rebuild_host.cpp links
+// rebuild_host.cpp and refit_host.cpp alone.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/srt_amd.h"
+#include "rebuild_rule.hpp"
+#include "refit_host.hpp"
+
+namespace srt {
+namespace rebuild {
+
+constexpr int kSummaryInts = kHeightBins + 2;  // what a rebuild reads back: the counts, the heights, the pairs
+
+// Rule 1 and 2: the scene box and the key of every triangle, in input order.
+void SceneBox(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, float lo[3], float hi[3]);
+void Keys(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t* keys);
+
+// ceil(log2 n) + 30: the depth no tree of the rule exceeds (n >= 1).
+int DepthBound(uint32_t n_tris);
+
+// srt_bvh_build_lbvh without the error string's global.
+int BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, srt_bvh_node* nodes_out,
+              srt_triangle* tris_out, uint32_t* order_out, std::string* err);
+
+// The argument contract, before any device is touched.  `refit` / `enabled`: what the object was created with
+// and whether srt_query_enable_rebuild ran; first_index: of BVH record 0.
+int CheckEnable(bool have_object, bool refit, uint32_t n_bvhs, uint32_t first_index, uint32_t n_tris, std::string* err);
+int CheckRebuild(bool have_object, bool refit, bool enabled, const void* verts_dev, uint32_t n_verts, uint32_t want_verts,
+                 std::string* err);
+
+// The schedule refit::BuildSchedule would make of a tree with counts[h] pairs at height h (`order` stays empty:
+// the device wrote it).  false when the counts do not add up to n_pairs or a level under the last is empty.
+bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out);
+
+}  // namespace rebuild
+}  // namespace srt

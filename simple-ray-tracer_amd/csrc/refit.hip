@@ -38,6 +38,34 @@ int Attach(srt_query* q, const query::Layout& lay, const srt_triangle* tris, uin
   return SRT_OK;
 }
 
+int Enqueue(srt_query* q, const srt_vertex* verts_dev) {
+  STAGE_HIP_OK(hipSetDevice(q->device));
+  const Schedule& s = q->schedule;
+  RParams rp;
+  std::memset(&rp, 0, sizeof rp);
+  rp.pairs = q->d_pairs;
+  rp.roots = q->d_roots;
+  rp.tris = q->d_tris;
+  rp.triples = q->d_triples;
+  rp.order = q->d_schedule;
+  rp.tail_first = q->d_schedule + q->n_pairs;
+  rp.verts = reinterpret_cast<const float4*>(verts_dev);
+  rp.n_verts = q->n_verts;
+  rp.n_tris = q->n_tris;
+  rp.n_roots = q->n_bvhs + 1;
+  rp.tail_levels = s.heights - s.tail_begin;
+  hipLaunchKernelGGL(refit_tris_kernel, dim3((q->n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp);
+  STAGE_HIP_OK(hipGetLastError());
+  for (uint32_t h = 0; h < s.tail_begin; ++h) {
+    const uint32_t first = s.first[h], count = s.first[h + 1] - first;
+    hipLaunchKernelGGL(refit_level_kernel, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp, first, count);
+    STAGE_HIP_OK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(refit_tail_kernel, dim3(1), dim3(kBlock), 0, q->stream, rp);
+  STAGE_HIP_OK(hipGetLastError());
+  return SRT_OK;
+}
+
 }  // namespace refit
 }  // namespace srt
 
@@ -54,7 +82,6 @@ int srt_bvh_refit(const srt_bvh_record* bvhs, uint32_t n_bvhs, srt_bvh_node* nod
 }
 
 int srt_query_refit(srt_query* q, const srt_vertex* verts_dev, uint32_t n_verts) {
-  using srt::refit::kBlock;
   if (!q) return SRT_ERR_INVALID;
   if (!q->refit) {
     srt::SetError("srt_query_refit: the object was created without SRT_QUERY_REFIT");
@@ -68,31 +95,7 @@ int srt_query_refit(srt_query* q, const srt_vertex* verts_dev, uint32_t n_verts)
     srt::SetError("srt_query_refit: n_verts differs from the count at creation");
     return SRT_ERR_INVALID;
   }
-  STAGE_HIP_OK(hipSetDevice(q->device));
-  const srt::refit::Schedule& s = q->schedule;
-  srt::refit::RParams rp;
-  std::memset(&rp, 0, sizeof rp);
-  rp.pairs = q->d_pairs;
-  rp.roots = q->d_roots;
-  rp.tris = q->d_tris;
-  rp.triples = q->d_triples;
-  rp.order = q->d_schedule;
-  rp.tail_first = q->d_schedule + q->n_pairs;
-  rp.verts = reinterpret_cast<const float4*>(verts_dev);
-  rp.n_verts = n_verts;
-  rp.n_tris = q->n_tris;
-  rp.n_roots = q->n_bvhs + 1;
-  rp.tail_levels = s.heights - s.tail_begin;
-  hipLaunchKernelGGL(srt::refit::refit_tris_kernel, dim3((q->n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp);
-  STAGE_HIP_OK(hipGetLastError());
-  for (uint32_t h = 0; h < s.tail_begin; ++h) {
-    const uint32_t first = s.first[h], count = s.first[h + 1] - first;
-    hipLaunchKernelGGL(srt::refit::refit_level_kernel, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp,
-                       first, count);
-    STAGE_HIP_OK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(srt::refit::refit_tail_kernel, dim3(1), dim3(kBlock), 0, q->stream, rp);
-  STAGE_HIP_OK(hipGetLastError());
+  if (int rc = srt::refit::Enqueue(q, verts_dev)) return rc;
   ++q->refit_count;
   return SRT_OK;
 }

@@ -28,7 +28,7 @@ from . import _lib
 from ._lib import SrtError, check, lib
 
 __all__ = [
-    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "UploadModelDataToGPU",
+    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "build_lbvh", "UploadModelDataToGPU",
     "UpdateModelMatrix", "Camera", "InputState", "progressive_frame", "PointLight", "generate_noise", "glibc_rand", "SrtError",
     "NODE_DTYPE", "BVH_DTYPE", "MAT_DTYPE", "TRI_DTYPE", "VERT_DTYPE", "LIGHT_DTYPE", "RAY_DTYPE",
     "MODEL_LIGHTS", "SPHERE_LIGHTS", "REFERENCE_OBJECTS",
@@ -365,6 +365,31 @@ def refit_scene(scene: Scene, verts: np.ndarray) -> Scene:
     check(lib().srt_bvh_refit(_ptr(scene.bvhs), len(scene.bvhs), _ptr(nodes), len(nodes), _ptr(scene.tris), len(scene.tris),
                               _ptr(verts), len(verts)), "srt_bvh_refit")
     return dataclasses.replace(scene, bvhs=scene.bvhs.copy(), nodes=nodes, verts=verts)
+
+
+def build_lbvh(scene: Scene, verts: np.ndarray | None = None) -> tuple["Scene", np.ndarray]:
+    """The host mirror of the device rebuild (``srt_bvh_build_lbvh``, include/srt_rebuild.h): a copy of the one-model
+    ``scene`` at ``verts`` (as :func:`refit_scene` takes them; None: the scene's own) whose ``nodes`` are the linear
+    BVH of its triangles and whose ``tris`` are in that tree's order, and ``order``: position -> index in
+    ``scene.tris``.  ``Query(scene, refit=True, rebuild=True).rebuild(verts)`` builds the same tree on the device."""
+    import dataclasses
+
+    if len(scene.bvhs) != 1:
+        raise ValueError("build_lbvh takes a scene of one model")
+    verts = scene.verts if verts is None else np.asarray(verts)
+    if verts.dtype != VERT_DTYPE:
+        pos = np.asarray(verts, np.float32).reshape(len(scene.verts), 3)
+        verts = scene.verts.copy()
+        verts["pos"] = pos
+    verts = np.ascontiguousarray(verts).reshape(-1).copy()
+    n = len(scene.tris)
+    nodes, tris, order = np.zeros(max(2 * n - 1, 0), NODE_DTYPE), np.zeros(n, TRI_DTYPE), np.zeros(n, np.uint32)
+    check(lib().srt_bvh_build_lbvh(_ptr(scene.tris), n, _ptr(verts), len(verts), _ptr(nodes), _ptr(tris), _ptr(order)),
+          "srt_bvh_build_lbvh")
+    bvhs = scene.bvhs.copy()
+    bvhs[0]["first_index"], bvhs[0]["count"] = 0, len(nodes)
+    tri_input = None if scene.tri_input is None else scene.tri_input[order]
+    return dataclasses.replace(scene, bvhs=bvhs, nodes=nodes, tris=tris, verts=verts, tri_input=tri_input), order
 
 
 # ---------------------------------------------------------------------------

@@ -354,6 +354,16 @@ _SCENE_REFIT_SIGS = {
 }
 SCENE_REFIT_SYMBOLS = tuple(_SCENE_REFIT_SIGS)
 
+# include/srt_rebuild.h: the device LBVH rebuild of a query object and its host mirror (its own header and version)
+_REBUILD_SIGS = {
+    "srt_rebuild_abi_version": (C.c_int, []),
+    "srt_query_enable_rebuild": (C.c_int, [P]),
+    "srt_query_rebuild": (C.c_int, [P, P, C.c_uint32]),
+    "srt_query_tri_order": (C.c_int, [P, P, C.c_uint32]),
+    "srt_bvh_build_lbvh": (C.c_int, [P, C.c_uint32, P, C.c_uint32, P, P, P]),
+}
+REBUILD_SYMBOLS = tuple(_REBUILD_SIGS)
+
 _lib = None
 
 
@@ -389,7 +399,7 @@ def lib() -> C.CDLL:
                                   + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
                                   + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
                                   + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
-                                  + list(_SCENE_REFIT_SIGS.items())):
+                                  + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

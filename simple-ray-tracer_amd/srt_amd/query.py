@@ -13,7 +13,7 @@ import numpy as np
 
 from . import RAY_DTYPE, VERT_DTYPE, Scene, _ptr
 from ._lib import SRT_QUERY_REFIT, check, lib
-from ._stage import _Stage, rays_arg
+from ._stage import _Stage, rays_arg, verts_arg
 
 __all__ = ["Query", "Hits", "HIT_DTYPE", "MISS"]
 
@@ -74,20 +74,31 @@ class Query(_Stage):
     it behaves as if it ran on the current stream, whichever that is at the time of the call.
 
     ``refit=True`` (``SRT_QUERY_REFIT``, include/srt_refit.h) also uploads the vertex indices and a refit
-    schedule, so :meth:`refit` can move the object to new vertex positions on the device.
+    schedule, so :meth:`refit` can move the object to new vertex positions on the device.  ``rebuild=True`` (with
+    ``refit=True``, one model; include/srt_rebuild.h) also allocates what :meth:`rebuild` needs to give the object a
+    new tree on the device.
     """
 
     _prefix = "srt_query"
 
-    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False):
+    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False, rebuild: bool = False):
         super().__init__(device, stream)
+        if rebuild and not refit:
+            raise ValueError("rebuild=True needs refit=True (include/srt_rebuild.h)")
         s = scene
         args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
                 len(s.verts))
+        self._n_tris = len(s.tris)
         if refit:
             self._create(*args, SRT_QUERY_REFIT, name="create_ex")
         else:
             self._create(*args)
+        if rebuild:
+            try:
+                self.enable_rebuild()
+            except Exception:
+                self.close()
+                raise
 
     # -- state ----------------------------------------------------------------
     def set_bvh_count(self, bvh_count: int):
@@ -115,6 +126,33 @@ class Query(_Stage):
                              "(srt_vertex fields)")
         self._run(lambda: lib().srt_query_refit(self.handle, C.c_void_p(verts.data_ptr()), verts.shape[0]),
                   "srt_query_refit")
+
+    # -- rebuild --------------------------------------------------------------
+    def enable_rebuild(self):
+        """``srt_query_enable_rebuild``: allocates what :meth:`rebuild` needs (``Query(..., rebuild=True)`` calls it)."""
+        check(lib().srt_query_enable_rebuild(self.handle), "srt_query_enable_rebuild")
+
+    def rebuild(self, verts):
+        """A new tree over the triangles at ``verts`` (``srt_query_rebuild``, include/srt_rebuild.h): a linear BVH
+        built on the device.  ``verts`` as :meth:`refit` takes them.  Ordered with the queries as ``closest`` is, but
+        not enqueue-only: the call synchronises the object's stream once.  ``Hits.triangle`` keeps meaning the
+        scene's triangle index."""
+        import torch
+        if isinstance(verts, np.ndarray):
+            host = np.ascontiguousarray(verts, dtype=VERT_DTYPE).view(np.float32).reshape(-1, 8)
+            self.rebuild(torch.from_numpy(host).to(f"cuda:{self.device}"))
+            self.synchronize()  # the upload may go once the kernels have read it
+            return
+        verts_arg(verts, self.device)
+        self._run(lambda: lib().srt_query_rebuild(self.handle, C.c_void_p(verts.data_ptr()), verts.shape[0]),
+                  "srt_query_rebuild")
+
+    def tri_order(self) -> np.ndarray:
+        """Position -> scene triangle index of the device's triangle records (``srt_query_tri_order``: a test and
+        debug readback; synchronises).  The identity before any rebuild."""
+        out = np.zeros(self._n_tris, np.uint32)
+        check(lib().srt_query_tri_order(self.handle, _ptr(out), len(out)), "srt_query_tri_order")
+        return out
 
     def layout(self):
         """The device arrays ``(pairs, roots, tris)`` of csrc/query_host.hpp's layout as uint32 ``[n, 4]`` numpy

@@ -2,7 +2,7 @@
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
                               [--max-depth D] [--out frame.png] [--denoise] [--albedo] [--orbit K] [--spin DEG] [--variance]
-                              [--wave A [--orbit K [--albedo]]]
+                              [--wave A [--orbit K [--albedo] [--rebuild-every K]]]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -54,7 +54,12 @@ def main():
                          "go to the renderer (bound once with refit=True, then Compute.refit on the device: "
                          "include/srt_scene_refit.h), the query, the temporal object, whose history follows the "
                          "surface (include/srt_temporal_deform.h), and with --albedo the surface object")
+    ap.add_argument("--rebuild-every", type=int, default=0, metavar="K",
+                    help="with --wave A --orbit N: every K-th frame the guide query gets a new tree, built on the device "
+                         "(Query(scene, refit=True, rebuild=True).rebuild, include/srt_rebuild.h), and is refit otherwise")
     a = ap.parse_args()
+    if a.rebuild_every and (a.rebuild_every < 0 or not (a.wave and a.orbit)):
+        ap.error("--rebuild-every K (K > 0) needs --wave A --orbit N")
     if a.wave and a.scene == "spheres":
         ap.error("--wave A needs a mesh scene")
     if a.wave and a.orbit and a.spin:
@@ -93,7 +98,7 @@ def main():
     if a.orbit:
         try:
             t0 = time.perf_counter()
-            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance, a.wave, a.albedo)
+            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance, a.wave, a.albedo, a.rebuild_every)
             dt = time.perf_counter() - t0
         finally:
             r.close()
@@ -178,7 +183,7 @@ def spin_frame(scene, degrees):
     return m.T.reshape(16).astype(np.float32)
 
 
-def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False):
+def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False, rebuild_every=0):
     """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
     (degrees per frame) under a still camera while the first model turns, or with `wave` (the amplitude) under a
     still camera while the wave's phase advances -- the per-frame calls of a deforming mesh, all on the device
@@ -204,7 +209,7 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo
     cam, c = setup.camera, r.compute
     acc_ptr, _ = c.image_pointers()
     with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, \
-            Query(setup.scene, refit=bool(wave)) as q, \
+            Query(setup.scene, refit=bool(wave), rebuild=bool(rebuild_every)) as q, \
             (Surface(setup.scene, refit=True) if albedo else contextlib.nullcontext()) as surf:
         q.set_bvh_count(setup.bvh_count)
         if wave:
@@ -225,7 +230,10 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo
                 verts = R.wave_vertices(setup.scene.verts, wave, WAVE_PHASE_STEP * k)
                 vdev = torch.from_numpy(np.ascontiguousarray(verts).view(np.float32).reshape(-1, 8)).to(f"cuda:{r.compute.device}")
                 c.refit(vdev)
-                q.refit(vdev)
+                if rebuild_every and k % rebuild_every == rebuild_every - 1:
+                    q.rebuild(vdev)  # a new tree for the guide; its hits keep the scene's triangle indices
+                else:
+                    q.refit(vdev)
                 tp.set_vertices(vdev)
                 if albedo:
                     surf.refit(vdev)
