@@ -1,5 +1,6 @@
-// srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h and include/srt_rebuild.h:
-// srt::Query, RAII over the C ABI with the same method names, AssetUtils::RefitBVH and AssetUtils::BuildLBVH.
+// srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h, include/srt_rebuild.h and
+// include/srt_rebuild_leaf.h: srt::Query, RAII over the C ABI with the same method names, AssetUtils::RefitBVH and
+// AssetUtils::BuildLBVH.
 // Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
@@ -10,6 +11,7 @@
 
 #include "../srt_query.h"
 #include "../srt_rebuild.h"
+#include "../srt_rebuild_leaf.h"
 #include "../srt_refit.h"
 
 namespace srt {
@@ -51,6 +53,8 @@ class Query {
   // builds a linear BVH over the triangles at `verts_dev` on the device (it synchronises the stream once).
   void EnableRebuild() { Check(srt_query_enable_rebuild(q_), "srt_query_enable_rebuild"); }
   void Rebuild(const srt_vertex* verts_dev, uint32_t n) { Check(srt_query_rebuild(q_, verts_dev, n), "srt_query_rebuild"); }
+  // include/srt_rebuild_leaf.h: from the next Rebuild on, subtrees of at most `max_leaf` triangles (1..255) are leaves.
+  void SetRebuildLeaf(uint32_t max_leaf) { Check(srt_query_set_rebuild_leaf(q_, max_leaf), "srt_query_set_rebuild_leaf"); }
   // Device pointers; both only enqueue on the query's stream.
   void closest(const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
     Check(srt_query_closest(q_, rays_dev, n, hits_dev), "srt_query_closest");
@@ -89,6 +93,16 @@ inline void BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_verte
                       srt_bvh_node* nodes_out, srt_triangle* tris_out, uint32_t* order_out) {
   if (int rc = srt_bvh_build_lbvh(tris, n_tris, verts, n_verts, nodes_out, tris_out, order_out))
     throw std::runtime_error("srt_bvh_build_lbvh failed with status " + std::to_string(rc) + ": " + srt_last_error());
+}
+
+// srt_bvh_build_lbvh_leaf: the same with subtrees of at most `max_leaf` triangles collapsed into leaves; returns the
+// number of nodes written (2m + 1; nodes_out has room for 2 * n_tris - 1).
+inline uint32_t BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t max_leaf,
+                          srt_bvh_node* nodes_out, srt_triangle* tris_out, uint32_t* order_out) {
+  uint32_t n_nodes = 0;
+  if (int rc = srt_bvh_build_lbvh_leaf(tris, n_tris, verts, n_verts, max_leaf, nodes_out, &n_nodes, tris_out, order_out))
+    throw std::runtime_error("srt_bvh_build_lbvh_leaf failed with status " + std::to_string(rc) + ": " + srt_last_error());
+  return n_nodes;
 }
 
 }  // namespace AssetUtils

@@ -28,7 +28,8 @@
  *                  runs the refit kernels over the new schedule for this step.
  * n == 1 keeps a leaf root (the rebuild reduces to a refit); n == 2 is one pair of leaves.
  *
- * Out of scope: leaves of several triangles -- no collapsing and no SAH; a changing n_verts or triangle list.
+ * Out of scope: SAH (leaves of several triangles by collapsing subtrees: srt_rebuild_leaf.h); a changing n_verts or
+ * triangle list.
  *
  * Additive to srt_amd.h, srt_query.h and srt_refit.h (their ABI versions are unchanged); versioned on its own.
  */

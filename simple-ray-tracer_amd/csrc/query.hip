@@ -258,6 +258,10 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   else if (n == "rebuild.bytes") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->bytes) : 0;
   else if (n == "rebuild.launches") *v = q->rebuild ? q->rebuild->launches : 0;
   else if (n == "rebuild.depth") *v = q->rebuild ? q->rebuild->depth : 0;
+  else if (n == "rebuild.leaf") *v = q->rebuild ? (int)q->rebuild->max_leaf : 0;
+  else if (n == "rebuild.max_leaf") *v = q->rebuild ? (int)q->rebuild->largest_leaf : 0;
+  else if (n == "rebuild.pairs") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->pairs) : 0;
+  else if (n == "rebuild.leaf_bytes") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->leaf_bytes) : 0;
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }

@@ -34,6 +34,15 @@ struct State {
   int count = 0, launches = 0, depth = 0;
   uint32_t summary[kSummaryInts] = {};
   std::vector<uint32_t> tail_first;  // host copy of the tail's level offsets while their upload is in flight
+  // srt_query_set_rebuild_leaf (include/srt_rebuild_leaf.h); allocated by the first value above 1
+  uint32_t max_leaf = 1;             // the setting, for the next rebuild
+  stage::DevPtr<uint4> d_split;      // n - 1: first, last, gamma, survives
+  stage::DevPtr<uint32_t> d_flags, d_rank;  // n each: the scan's input and output
+  stage::DevPtr<uint32_t> d_leafsum;        // m, the largest leaf count
+  stage::DevPtr<uint8_t> d_scan_temp;
+  size_t scan_temp_bytes = 0, leaf_bytes = 0;
+  uint32_t leaf_summary[2] = {};     // what the last collapsed rebuild read back from d_leafsum
+  uint32_t pairs = 0, largest_leaf = 0;  // of the last rebuild's tree
 };
 
 }  // namespace rebuild

@@ -1,8 +1,11 @@
 // rebuild.hip -- the device rebuild of include/srt_rebuild.h: the rebuild data of a query object, the launches of
 // rebuild.hpp's kernels around hipcub's radix sort, the one readback, the new schedule and stack plan, the
-// refit that fills the boxes, and the hit remap.  A translation unit of its own beside query.hip and refit.hip.
+// refit that fills the boxes, and the hit remap; and include/srt_rebuild_leaf.h's max_leaf, which puts a range kernel,
+// hipcub's scan and an emit kernel in the hierarchy kernel's place.  A translation unit of its own beside query.hip
+// and refit.hip.
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
+#include <hipcub/device/device_scan.hpp>
 
 #include <cstring>
 #include <string>
@@ -10,6 +13,7 @@
 #include <vector>
 
 #include "../../include/srt_rebuild.h"
+#include "../../include/srt_rebuild_leaf.h"
 #include "query_object.hpp"
 #include "rebuild.hpp"
 #include "rebuild_host.hpp"
@@ -27,6 +31,11 @@ uint32_t Blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 hipError_t Sort(State& st, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
   return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)st.d_keys_in.get(), st.d_keys.get(),
                                             (const uint32_t*)st.d_vals_in.get(), st.d_order.get(), n, 0, kKeyBits, stream);
+}
+
+// rank = the exclusive sum of the n survival flags (the last is 0, so rank[n - 1] is the number of survivors)
+hipError_t Scan(const uint32_t* flags, uint32_t* rank, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
+  return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, flags, rank, (int)n, stream);
 }
 
 }  // namespace
@@ -64,6 +73,37 @@ int Enable(srt_query* q) {
   return SRT_OK;
 }
 
+// What the collapse adds on the device, at the first max_leaf above 1 (a mesh of one triangle never needs it).
+int SetLeaf(srt_query* q, uint32_t max_leaf) {
+  State& st = *q->rebuild;
+  const uint32_t n = q->n_tris;
+  if (max_leaf > 1 && n > 1 && !st.d_flags) {
+    STAGE_HIP_OK(hipSetDevice(q->device));
+    stage::DevPtr<uint4> split;
+    stage::DevPtr<uint32_t> flags, rank, leafsum;
+    stage::DevPtr<uint8_t> scan_temp;
+    const size_t per_tri = sizeof(uint32_t) * (size_t)n, sb = sizeof(uint4) * (size_t)(n - 1);
+    STAGE_HIP_OK(split.Alloc(sb));
+    STAGE_HIP_OK(flags.Alloc(per_tri));
+    STAGE_HIP_OK(rank.Alloc(per_tri));
+    STAGE_HIP_OK(leafsum.Alloc(2 * sizeof(uint32_t)));
+    size_t temp = 0;
+    STAGE_HIP_OK(Scan(flags, rank, n, q->stream, nullptr, temp));  // the size only: nothing is enqueued
+    temp = temp ? temp : 16;
+    STAGE_HIP_OK(scan_temp.Alloc(temp));
+    // (every allocation succeeded: only now does the state change)
+    st.scan_temp_bytes = temp;
+    st.d_flags = std::move(flags);
+    st.d_rank = std::move(rank);
+    st.d_split = std::move(split);
+    st.d_leafsum = std::move(leafsum);
+    st.d_scan_temp = std::move(scan_temp);
+    st.leaf_bytes = sb + 2 * per_tri + 2 * sizeof(uint32_t) + st.scan_temp_bytes;
+  }
+  st.max_leaf = max_leaf;
+  return SRT_OK;
+}
+
 int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   STAGE_HIP_OK(hipSetDevice(q->device));
   State& st = *q->rebuild;
@@ -72,10 +112,15 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
     if (int rc = refit::Enqueue(q, verts_dev)) return rc;
     st.launches = (int)q->schedule.launches;
     st.depth = 0;
+    st.pairs = 0;
+    st.largest_leaf = 1;
     ++st.count;
     return SRT_OK;
   }
-  const uint32_t n_pairs = n - 1;
+  const uint32_t n_pairs = n - 1;       // of Karras' hierarchy, and the pair array's capacity
+  const uint32_t max_leaf = st.max_leaf;
+  const bool collapse = max_leaf > 1;   // rules 4a-4c; false: exactly srt_rebuild.h's launches
+  const bool leaf_root = n <= max_leaf; // m == 0: the sort, the root, the refit
   const bool first_time = st.count == 0;
   if (first_time) {
     // the LBVH's arrays take the object's place; the state keeps the creation-order triples for every later
@@ -83,11 +128,6 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
     std::swap(st.d_pairs, q->d_pairs);
     std::swap(st.d_triples, q->d_triples);
     std::swap(st.d_schedule, q->d_schedule);
-    const size_t pb = 4 * sizeof(float4) * (size_t)n_pairs, tb = sizeof(uint4) * (size_t)n;
-    q->scene_bytes = q->scene_bytes - q->pairs_bytes + pb;
-    q->pairs_bytes = pb;
-    q->n_pairs = n_pairs;
-    q->refit_bytes = tb + sizeof(uint32_t) * ((size_t)n_pairs + kHeightBins + 1);
   }
   BParams bp;
   std::memset(&bp, 0, sizeof bp);
@@ -111,6 +151,13 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   bp.n_verts = q->n_verts;
   bp.n_tris = n;
   bp.box_blocks = Blocks(n) < kBoxBlocks ? Blocks(n) : kBoxBlocks;
+  if (collapse) {
+    bp.split = st.d_split;
+    bp.flags = st.d_flags;
+    bp.rank = st.d_rank;
+    bp.leafsum = st.d_leafsum;
+    bp.max_leaf = max_leaf;
+  }
   hipStream_t s = q->stream;
   int launches = 0;
 #define REBUILD_LAUNCH(kernel, blocks)                                            \
@@ -126,33 +173,61 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   size_t temp = st.temp_bytes;
   STAGE_HIP_OK(Sort(st, n, s, st.d_temp, temp));
   ++launches;  // (the sort's own launches are hipcub's business: counted as one)
-  REBUILD_LAUNCH(karras_kernel, Blocks(n_pairs));
-  REBUILD_LAUNCH(permute_kernel, Blocks(n));
-  REBUILD_LAUNCH(climb_kernel, Blocks(n));
-  REBUILD_LAUNCH(schedule_kernel, Blocks(n_pairs));
+  if (leaf_root) {
+    // no pair: the positions' order and the root are the tree (pair 0, which srt_query_copy_layout still copies,
+    // keeps nothing of the tree before)
+    REBUILD_LAUNCH(permute_kernel, Blocks(n));
+    REBUILD_LAUNCH(root_leaf_kernel, 1);
+    STAGE_HIP_OK(hipMemsetAsync(q->d_pairs, 0, 4 * sizeof(float4), s));
+  } else if (collapse) {
+    REBUILD_LAUNCH(range_kernel, Blocks(n));
+    size_t scan_temp = st.scan_temp_bytes;
+    STAGE_HIP_OK(Scan(st.d_flags, st.d_rank, n, s, st.d_scan_temp, scan_temp));
+    ++launches;  // (hipcub's business again: counted as one)
+    REBUILD_LAUNCH(emit_kernel, Blocks(n_pairs));
+    REBUILD_LAUNCH(permute_kernel, Blocks(n));
+    REBUILD_LAUNCH(climb_kernel<true>, Blocks(n));
+    REBUILD_LAUNCH(schedule_kernel<true>, Blocks(n_pairs));
+  } else {
+    REBUILD_LAUNCH(karras_kernel, Blocks(n_pairs));
+    REBUILD_LAUNCH(permute_kernel, Blocks(n));
+    REBUILD_LAUNCH(climb_kernel<false>, Blocks(n));
+    REBUILD_LAUNCH(schedule_kernel<false>, Blocks(n_pairs));
+  }
 #undef REBUILD_LAUNCH
-  // the one synchronisation: the pair counts per height
+  // the one synchronisation: the pair counts per height, and of a collapsed tree its pairs and its largest leaf
   STAGE_HIP_OK(hipMemcpyAsync(st.summary, st.d_zeroed, sizeof(uint32_t) * kHeightBins, hipMemcpyDeviceToHost, s));
+  if (collapse && !leaf_root)
+    STAGE_HIP_OK(hipMemcpyAsync(st.leaf_summary, st.d_leafsum, sizeof st.leaf_summary, hipMemcpyDeviceToHost, s));
   STAGE_HIP_OK(hipStreamSynchronize(s));
   if (first_time) {  // nothing enqueued reads the replaced tree any more
     st.d_pairs.Free();
     st.d_schedule.Free();
   }
+  const uint32_t m = leaf_root ? 0u : (collapse ? st.leaf_summary[0] : n_pairs);
+  const uint32_t largest = leaf_root ? n : (collapse ? st.leaf_summary[1] : 1u);
   refit::Schedule sched;
-  if (!ScheduleFromCounts(st.summary, kHeightBins, n_pairs, &sched)) {
+  if ((collapse && !leaf_root && !LeafSummaryValid(m, largest, n, max_leaf)) ||
+      !ScheduleFromCounts(st.summary, kHeightBins, m, &sched)) {
     srt::SetError("srt_query_rebuild: the device hierarchy is not a tree over every triangle (non-finite vertices?)");
     return SRT_ERR_STATE;
   }
   st.summary[kHeightBins] = sched.heights;
-  st.summary[kHeightBins + 1] = n_pairs;
+  st.summary[kHeightBins + 1] = m;
+  // the object describes the tree built: the first m pairs of the array's n - 1
+  const size_t pb = 4 * sizeof(float4) * (size_t)(m ? m : 1u), tb = sizeof(uint4) * (size_t)n;
+  q->scene_bytes = q->scene_bytes - q->pairs_bytes + pb;
+  q->pairs_bytes = pb;
+  q->n_pairs = m;
+  q->refit_bytes = tb + sizeof(uint32_t) * ((size_t)m + kHeightBins + 1);
   st.tail_first.assign(sched.first.begin() + sched.tail_begin, sched.first.end());
-  STAGE_HIP_OK(hipMemcpyAsync(q->d_schedule + n_pairs, st.tail_first.data(), sizeof(uint32_t) * st.tail_first.size(),
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_schedule + m, st.tail_first.data(), sizeof(uint32_t) * st.tail_first.size(),
                               hipMemcpyHostToDevice, s));
   q->schedule = std::move(sched);
-  // the stack plan of the new tree: one-triangle leaves, depth == heights
+  // the stack plan of the new tree: its largest leaf, depth == heights
   query::Layout shape;
-  shape.n_pairs = n_pairs;
-  shape.max_leaf = 1;
+  shape.n_pairs = m;
+  shape.max_leaf = largest;
   shape.depth = (int)q->schedule.heights;
   const query::StackPlan plan = query::PlanStack(shape, n);
   const query::StackPlan old = q->plan;
@@ -166,6 +241,8 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   if (int rc = refit::Enqueue(q, verts_dev)) return rc;
   st.launches = launches + (int)q->schedule.launches;
   st.depth = shape.depth;
+  st.pairs = m;
+  st.largest_leaf = largest;
   ++st.count;
   return SRT_OK;
 }
@@ -191,6 +268,27 @@ int srt_bvh_build_lbvh(const srt_triangle* tris, uint32_t n_tris, const srt_vert
   const int rc = srt::rebuild::BuildLBVH(tris, n_tris, verts, n_verts, nodes_out, tris_out, order_out, &err);
   if (rc) srt::SetError(err);
   return rc;
+}
+
+int srt_rebuild_leaf_abi_version(void) { return SRT_REBUILD_LEAF_ABI_VERSION; }
+
+int srt_bvh_build_lbvh_leaf(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts,
+                            uint32_t max_leaf, srt_bvh_node* nodes_out, uint32_t* n_nodes_out, srt_triangle* tris_out,
+                            uint32_t* order_out) {
+  std::string err;
+  const int rc = srt::rebuild::BuildLBVHLeaf(tris, n_tris, verts, n_verts, max_leaf, nodes_out, n_nodes_out, tris_out,
+                                             order_out, &err);
+  if (rc) srt::SetError(err);
+  return rc;
+}
+
+int srt_query_set_rebuild_leaf(srt_query* q, uint32_t max_leaf) {
+  std::string err;
+  if (int rc = srt::rebuild::CheckSetLeaf(q != nullptr, q && q->rebuild, max_leaf, &err)) {
+    srt::SetError(err);
+    return rc;
+  }
+  return srt::rebuild::SetLeaf(q, max_leaf);
 }
 
 int srt_query_enable_rebuild(srt_query* q) {

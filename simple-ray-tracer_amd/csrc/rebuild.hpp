@@ -14,6 +14,16 @@
 // schedule_kernel: a counting sort of the pairs by height into the format refit.hpp reads (the order inside a
 //   height is free); a block takes its share of each height with one atomic per height.
 // remap_kernel: one lane per hit; the position srt_query_closest reported becomes the creation index.
+//
+// With max_leaf > 1 (include/srt_rebuild_leaf.h) range_kernel, hipcub's exclusive scan and emit_kernel stand in for
+// karras_kernel, and the LEAF instances of climb_kernel and schedule_kernel work in rank space over the m pairs
+// the scan counted -- m stays on the device (leafsum[0]) until the rebuild's one readback.
+// range_kernel: one lane per Karras node; its split (first, last, gamma) and whether it survives the collapse, and
+//   one lane per position marks it as owned by no pair.
+// emit_kernel: one lane per surviving node; the .w fields of pair rank(i), the parents of its internal children in
+//   rank space, the owning pair of each leaf's first position, and the block's largest leaf count through one
+//   atomic max.  Only the first position of a leaf starts a climb; the marks of every other position stay.
+// root_leaf_kernel: n <= max_leaf; the leaf root (0, n).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,7 +59,16 @@ struct BParams {
   uint32_t* cursor;         // kHeightBins, zero at launch
   uint32_t* schedule;       // n - 1 pair indices by height
   uint32_t n_verts, n_tris, box_blocks;
+  // max_leaf > 1 only (null / 0 otherwise); then `parent` is [0, n - 1): of pairs, by rank; [n - 1, 2n - 1): the pair
+  // that owns the leaf starting at the position, or kNoOwner
+  uint4* split;             // n - 1: first, last, gamma, survives
+  uint32_t* flags;          // n: survives, and a 0 past the last node so that the scan's last output is m
+  const uint32_t* rank;     // n: the exclusive sum of flags; rank[n - 1] == m
+  uint32_t* leafsum;        // m, the largest leaf count
+  uint32_t max_leaf;
 };
+
+constexpr uint32_t kNoOwner = 0xFFFFFFFFu;  // (not below any pair count: such a position starts no climb)
 
 struct Span3 {
   float lo[3], hi[3];
@@ -200,16 +219,26 @@ __global__ __launch_bounds__(256) void permute_kernel(BParams bp) {
   bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];  // (a whole record: one 16-B load, one 16-B store)
 }
 
+// The pairs of the tree being built: n - 1, or with LEAF the m the scan counted (never more than n - 1).
+template <bool LEAF>
+__device__ __forceinline__ uint32_t pair_count(const BParams& bp) {
+  if (!LEAF) return bp.n_tris - 1u;
+  const uint32_t m = bp.leafsum[0];
+  return m < bp.n_tris - 1u ? m : bp.n_tris - 1u;
+}
+
+template <bool LEAF>
 __global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
   __shared__ uint32_t bins[kHeightBins];
   if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
   __syncthreads();
   const uint32_t n = bp.n_tris;  // >= 2
-  const uint32_t leaf = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n_pairs = pair_count<LEAF>(bp);
+  const uint32_t leaf = blockIdx.x * kBlock + threadIdx.x;  // (LEAF: a position; the first of a leaf has an owner)
   if (leaf < n) {
     uint32_t p = bp.parent[n - 1 + leaf];
     uint32_t val = 0u;  // of a child: 0 for a leaf, its pair's height + 1 for an internal node
-    for (int step = 0; step < kHeightBins && p < n - 1; ++step) {
+    for (int step = 0; step < kHeightBins && p < n_pairs; ++step) {
       const uint32_t old = __hip_atomic_exchange(bp.arrive + p, val + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (old == 0u) break;  // the first to arrive: the other side's lane carries on from here
       uint32_t h = old - 1u > val ? old - 1u : val;
@@ -225,11 +254,12 @@ __global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
   if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) atomicAdd(bp.counts + threadIdx.x, bins[threadIdx.x]);
 }
 
+template <bool LEAF>
 __global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
   __shared__ uint32_t bins[kHeightBins], base[kHeightBins];
   if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
   __syncthreads();
-  const uint32_t n_pairs = bp.n_tris - 1u;
+  const uint32_t n_pairs = pair_count<LEAF>(bp);
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   uint32_t h = 0u, rank = 0u;
   if (p < n_pairs) {
@@ -247,6 +277,80 @@ __global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
   if (p < n_pairs) {
     const uint32_t at = base[h] + rank;
     if (at < n_pairs) bp.schedule[at] = p;
+  }
+}
+
+// -- max_leaf > 1 ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void range_kernel(BParams bp) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;  // > max_leaf >= 2
+  if (i >= n) return;
+  if (i == 0) bp.leafsum[1] = 0u;  // the emit kernel's atomic max starts here
+  bp.parent[n - 1 + i] = kNoOwner;
+  uint32_t survives = 0u;
+  if (i + 1 < n) {
+    const Split sp = KarrasSplit(bp.keys, n, i);
+    survives = Survives(sp, bp.max_leaf) ? 1u : 0u;
+    bp.split[i] = make_uint4((uint32_t)sp.first, (uint32_t)sp.last, (uint32_t)sp.gamma, survives);
+  }
+  bp.flags[i] = survives;
+}
+
+// One slot of pair r; an index is < n - 1 (a node) or < n (a position) by construction, the clamps keep every store
+// inside its array.
+__device__ __forceinline__ uint32_t emit_slot(const BParams& bp, float4* rec, const Slot& s, uint32_t r) {
+  const uint32_t n = bp.n_tris;
+  if (s.count > 0u) {
+    const uint32_t pos = s.index < n ? s.index : n - 1u;
+    rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(pos));
+    rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(s.count));
+    bp.parent[n - 1u + pos] = r;
+    return s.count;
+  }
+  uint32_t c = bp.rank[s.index < n - 1u ? s.index : n - 2u];
+  c = c < n - 1u ? c : n - 2u;
+  rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c));
+  rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+  bp.parent[c] = r;
+  return 0u;
+}
+
+__global__ __launch_bounds__(256) void emit_kernel(BParams bp) {
+  __shared__ uint32_t largest;
+  if (threadIdx.x == 0) largest = 0u;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;
+  if (i == 0) {  // both root records reference pair 0 (node 0 survives: n > max_leaf), and m for the kernels after
+    const Child root{0u, false};
+    put_child(bp.roots, root);
+    put_child(bp.roots + 2, root);
+    bp.leafsum[0] = bp.rank[n - 1u];
+  }
+  if (i + 1 < n) {
+    const uint4 sp4 = bp.split[i];
+    if (sp4.w != 0u) {
+      Split sp;
+      sp.first = sp4.x;
+      sp.last = sp4.y;
+      sp.gamma = sp4.z;
+      uint32_t r = bp.rank[i];
+      r = r < n - 1u ? r : n - 2u;
+      float4* rec = bp.pairs + 4 * (size_t)r;
+      const uint32_t a = emit_slot(bp, rec, LeftSlot(sp, bp.max_leaf), r);
+      const uint32_t b = emit_slot(bp, rec + 2, RightSlot(sp, bp.max_leaf), r);
+      if ((a > b ? a : b) > 0u) atomicMax(&largest, a > b ? a : b);
+    }
+  }
+  __syncthreads();  // (every lane arrives)
+  if (threadIdx.x == 0 && largest != 0u) atomicMax(bp.leafsum + 1, largest);
+}
+
+__global__ __launch_bounds__(256) void root_leaf_kernel(BParams bp) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  for (int r = 0; r < 2; ++r) {  // the BVH record and the ghost root
+    bp.roots[2 * r] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+    bp.roots[2 * r + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(bp.n_tris));
   }
 }
 

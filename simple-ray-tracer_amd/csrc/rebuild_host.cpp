@@ -60,7 +60,14 @@ int DepthBound(uint32_t n_tris) {
 
 int BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, srt_bvh_node* nodes_out,
               srt_triangle* tris_out, uint32_t* order_out, std::string* err) {
-  if (!tris || !nodes_out || !tris_out || !order_out || (n_verts && !verts)) return Fail(err, "null argument");
+  uint32_t n_nodes = 0;  // 2 * n_tris - 1: every internal node survives
+  return BuildLBVHLeaf(tris, n_tris, verts, n_verts, 1, nodes_out, &n_nodes, tris_out, order_out, err);
+}
+
+int BuildLBVHLeaf(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t max_leaf,
+                  srt_bvh_node* nodes_out, uint32_t* n_nodes_out, srt_triangle* tris_out, uint32_t* order_out, std::string* err) {
+  if (!tris || !nodes_out || !n_nodes_out || !tris_out || !order_out || (n_verts && !verts)) return Fail(err, "null argument");
+  if (max_leaf == 0 || max_leaf > kMaxLeafLimit) return Fail(err, "srt_bvh_build_lbvh_leaf: max_leaf must be in [1, 255]");
   if (n_tris == 0) return Fail(err, "srt_bvh_build_lbvh: a tree needs at least one triangle");
   if (n_tris >= kMaxTris) return Fail(err, "srt_bvh_build_lbvh: 2^30 triangles or more", SRT_ERR_LIMIT);
   for (uint32_t i = 0; i < n_verts; ++i)
@@ -77,24 +84,35 @@ int BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts
     tris_out[p] = tris[order[p]];
     order_out[p] = order[p];
   }
-  // rule 4: the children of internal node i are nodes 2i + 1 and 2i + 2; node 0 is the root
-  const size_t n_nodes = 2 * (size_t)n_tris - 1;
+  // rule 4 with 4a-4c: every node's split, the survivors' ranks by increasing Karras index, then the children of
+  // survivor i at nodes 2 rank(i) + 1 and 2 rank(i) + 2; node 0 is the root.  With max_leaf == 1 every internal node
+  // survives and rank(i) == i.
+  const uint32_t n_internal = n_tris - 1;
+  std::vector<Split> split(n_internal);
+  std::vector<uint32_t> rank(n_internal);
+  uint32_t m = 0;
+  for (uint32_t i = 0; i < n_internal; ++i) {
+    split[i] = KarrasSplit(sorted.data(), n_tris, i);
+    rank[i] = m;
+    if (Survives(split[i], max_leaf)) ++m;
+  }
+  const size_t n_nodes = 2 * (size_t)m + 1;
   for (size_t i = 0; i < n_nodes; ++i) nodes_out[i] = srt_bvh_node{};
-  auto put = [&](size_t at, const Child& c) {
-    nodes_out[at].first_child_or_prim_index = c.leaf ? c.index : 2 * c.index + 1;
-    nodes_out[at].prim_count = c.leaf ? 1u : 0u;
+  auto put = [&](size_t at, const Slot& s) {
+    nodes_out[at].first_child_or_prim_index = s.count ? s.index : 2 * rank[s.index] + 1;
+    nodes_out[at].prim_count = s.count;
   };
-  if (n_tris == 1) {
-    put(0, Child{0, true});
+  if (n_tris <= max_leaf) {
+    put(0, Slot{0, n_tris});
   } else {
-    put(0, Child{0, false});
-    for (uint32_t i = 0; i + 1 < n_tris; ++i) {
-      Child l, r;
-      KarrasNode(sorted.data(), n_tris, i, &l, &r);
-      put(2 * (size_t)i + 1, l);
-      put(2 * (size_t)i + 2, r);
+    put(0, Slot{0, 0});
+    for (uint32_t i = 0; i < n_internal; ++i) {
+      if (!Survives(split[i], max_leaf)) continue;
+      put(2 * (size_t)rank[i] + 1, LeftSlot(split[i], max_leaf));
+      put(2 * (size_t)rank[i] + 2, RightSlot(split[i], max_leaf));
     }
   }
+  *n_nodes_out = (uint32_t)n_nodes;
   // rule 5: srt_refit.h's fold on the new topology (which also walks the tree: a malformed one fails here)
   srt_bvh_record rec{};
   return refit::RefitNodes(&rec, 1, nodes_out, (uint32_t)n_nodes, tris_out, n_tris, verts, n_verts, err);
@@ -118,6 +136,17 @@ int CheckRebuild(bool have_object, bool refit, bool enabled, const void* verts_d
     return Fail(err, "srt_query_rebuild: verts_dev must be a 16-byte aligned device pointer");
   if (n_verts != want_verts) return Fail(err, "srt_query_rebuild: n_verts differs from the count at creation");
   return SRT_OK;
+}
+
+int CheckSetLeaf(bool have_object, bool enabled, uint32_t max_leaf, std::string* err) {
+  if (!have_object) return Fail(err, "srt_query_set_rebuild_leaf: null object");
+  if (!enabled) return Fail(err, "srt_query_set_rebuild_leaf: rebuild is not enabled (srt_query_enable_rebuild)");
+  if (max_leaf == 0 || max_leaf > kMaxLeafLimit) return Fail(err, "srt_query_set_rebuild_leaf: max_leaf must be in [1, 255]");
+  return SRT_OK;
+}
+
+bool LeafSummaryValid(uint32_t m, uint32_t largest, uint32_t n_tris, uint32_t max_leaf) {
+  return m >= 1 && m <= n_tris - 1 && largest >= 1 && largest <= max_leaf;
 }
 
 bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out) {

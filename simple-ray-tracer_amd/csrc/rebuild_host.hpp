@@ -1,7 +1,8 @@
-// rebuild_host.hpp -- host-only parts of the device rebuild (include/srt_rebuild.h): the host mirror of the LBVH
-// (srt_bvh_build_lbvh), the argument contract of the two object calls, and the refit schedule and depth from the
-// pair counts per height the device reports.  No device, no HIP header: tests/cpp/test_rebuild_host.cpp links
-// rebuild_host.cpp and refit_host.cpp alone.
+// rebuild_host.hpp -- host-only parts of the device rebuild (include/srt_rebuild.h, include/srt_rebuild_leaf.h): the
+// host mirror of the LBVH (srt_bvh_build_lbvh, srt_bvh_build_lbvh_leaf), the argument contract of the object calls, and
+// the refit schedule and depth from the pair counts per height the device reports.  No device, no HIP header:
+// tests/cpp/test_rebuild_host.cpp and tests/cpp/test_rebuild_leaf_host.cpp link rebuild_host.cpp and refit_host.cpp
+// alone.
 #pragma once
 
 #include <cstddef>
@@ -29,15 +30,26 @@ int DepthBound(uint32_t n_tris);
 int BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, srt_bvh_node* nodes_out,
               srt_triangle* tris_out, uint32_t* order_out, std::string* err);
 
+// srt_bvh_build_lbvh_leaf (include/srt_rebuild_leaf.h) without the error string's global: rules 4a-4c on the same
+// keys, order and hierarchy.  Writes 2m + 1 nodes and that count; BuildLBVH is this with max_leaf == 1.
+int BuildLBVHLeaf(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t max_leaf,
+                  srt_bvh_node* nodes_out, uint32_t* n_nodes_out, srt_triangle* tris_out, uint32_t* order_out, std::string* err);
+
 // The argument contract, before any device is touched.  `refit` / `enabled`: what the object was created with
 // and whether srt_query_enable_rebuild ran; first_index: of BVH record 0.
 int CheckEnable(bool have_object, bool refit, uint32_t n_bvhs, uint32_t first_index, uint32_t n_tris, std::string* err);
 int CheckRebuild(bool have_object, bool refit, bool enabled, const void* verts_dev, uint32_t n_verts, uint32_t want_verts,
                  std::string* err);
+int CheckSetLeaf(bool have_object, bool enabled, uint32_t max_leaf, std::string* err);
 
 // The schedule refit::BuildSchedule would make of a tree with counts[h] pairs at height h (`order` stays empty:
-// the device wrote it).  false when the counts do not add up to n_pairs or a level under the last is empty.
+// the device wrote it).  false when the counts do not add up to n_pairs -- the pair count the caller has, n - 1 or
+// the collapsed tree's m as the device reported it -- or a level under the last is empty.
 bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out);
+
+// What a collapsed rebuild reads back beside the counts, checked before anything is planned from it: 1 <= m <= n - 1
+// pairs and a largest leaf in [1, max_leaf] (n > max_leaf >= 1).
+bool LeafSummaryValid(uint32_t m, uint32_t largest, uint32_t n_tris, uint32_t max_leaf);
 
 }  // namespace rebuild
 }  // namespace srt

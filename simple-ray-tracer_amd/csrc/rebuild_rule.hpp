@@ -1,5 +1,5 @@
-// rebuild_rule.hpp -- the rule of include/srt_rebuild.h as code both sides compile: the key of a triangle, the
-// common prefix of two positions and one node of Karras' hierarchy.  rebuild_host.cpp (the host mirror) and
+// rebuild_rule.hpp -- the rule of include/srt_rebuild.h and include/srt_rebuild_leaf.h as code both sides compile: the
+// key of a triangle, the common prefix of two positions, one node of Karras' hierarchy and the collapse of its subtrees.  rebuild_host.cpp (the host mirror) and
 // rebuild.hpp (the kernels) include this one text, so the two cannot drift.  No HIP header, no library call: selects,
 // single fp32 operations and integer arithmetic only (the build's flags keep them uncontracted and the division
 // correctly rounded).
@@ -61,8 +61,12 @@ struct Child {
 };
 
 // Internal node i (0 <= i < n - 1, n >= 2) of Karras' binary radix tree over keys[0 .. n): its range is [i, j] or
-// [j, i], split after position `gamma`; the left child covers the lower positions.
-SRT_RULE_HD void KarrasNode(const uint32_t* keys, int64_t n, int64_t i, Child* left, Child* right) {
+// [j, i] -- positions first .. last -- split after position `gamma`; the left child covers the lower positions.
+struct Split {
+  int64_t first, last, gamma;
+};
+
+SRT_RULE_HD Split KarrasSplit(const uint32_t* keys, int64_t n, int64_t i) {
   const int d = Prefix(keys, n, i, i + 1) - Prefix(keys, n, i, i - 1) < 0 ? -1 : 1;
   const int floor_prefix = Prefix(keys, n, i, i - d);
   int64_t lmax = 2;
@@ -77,12 +81,42 @@ SRT_RULE_HD void KarrasNode(const uint32_t* keys, int64_t n, int64_t i, Child* l
     if (Prefix(keys, n, i, i + (s + t) * d) > node_prefix) s += t;
     if (t <= 1) break;
   }
-  const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
-  const int64_t first = i < j ? i : j, last = i < j ? j : i;
-  left->index = (uint32_t)gamma;
-  left->leaf = first == gamma;
-  right->index = (uint32_t)(gamma + 1);
-  right->leaf = last == gamma + 1;
+  Split sp;
+  sp.gamma = i + s * d + (d < 0 ? -1 : 0);
+  sp.first = i < j ? i : j;
+  sp.last = i < j ? j : i;
+  return sp;
+}
+
+// Rule 4 with one-triangle leaves: the two children of internal node i.
+SRT_RULE_HD void KarrasNode(const uint32_t* keys, int64_t n, int64_t i, Child* left, Child* right) {
+  const Split sp = KarrasSplit(keys, n, i);
+  left->index = (uint32_t)sp.gamma;
+  left->leaf = sp.first == sp.gamma;
+  right->index = (uint32_t)(sp.gamma + 1);
+  right->leaf = sp.last == sp.gamma + 1;
+}
+
+// Rule 4a (include/srt_rebuild_leaf.h): an internal node survives iff its range holds more than max_leaf positions,
+// and a child range [a, b] of a surviving node is one leaf (a, b - a + 1) iff it holds at most max_leaf; otherwise it
+// is the internal node `a` (a right child) or `b` (a left child), which Karras' numbering puts at the split.
+constexpr uint32_t kMaxLeafLimit = 255;  // leaf counts stay below 256: PlanStack's 2-dword packing
+
+SRT_RULE_HD bool Survives(const Split& sp, uint32_t max_leaf) { return sp.last - sp.first + 1 > (int64_t)max_leaf; }
+
+struct Slot {
+  uint32_t index;  // a leaf's first position, or the Karras index of an internal node
+  uint32_t count;  // a leaf's triangles; 0: internal
+};
+
+SRT_RULE_HD Slot LeftSlot(const Split& sp, uint32_t max_leaf) {
+  const int64_t c = sp.gamma - sp.first + 1;
+  return c <= (int64_t)max_leaf ? Slot{(uint32_t)sp.first, (uint32_t)c} : Slot{(uint32_t)sp.gamma, 0u};
+}
+
+SRT_RULE_HD Slot RightSlot(const Split& sp, uint32_t max_leaf) {
+  const int64_t c = sp.last - sp.gamma;
+  return c <= (int64_t)max_leaf ? Slot{(uint32_t)(sp.gamma + 1), (uint32_t)c} : Slot{(uint32_t)(sp.gamma + 1), 0u};
 }
 
 }  // namespace rebuild

@@ -367,11 +367,13 @@ def refit_scene(scene: Scene, verts: np.ndarray) -> Scene:
     return dataclasses.replace(scene, bvhs=scene.bvhs.copy(), nodes=nodes, verts=verts)
 
 
-def build_lbvh(scene: Scene, verts: np.ndarray | None = None) -> tuple["Scene", np.ndarray]:
+def build_lbvh(scene: Scene, verts: np.ndarray | None = None, max_leaf: int = 1) -> tuple["Scene", np.ndarray]:
     """The host mirror of the device rebuild (``srt_bvh_build_lbvh``, include/srt_rebuild.h): a copy of the one-model
     ``scene`` at ``verts`` (as :func:`refit_scene` takes them; None: the scene's own) whose ``nodes`` are the linear
     BVH of its triangles and whose ``tris`` are in that tree's order, and ``order``: position -> index in
-    ``scene.tris``.  ``Query(scene, refit=True, rebuild=True).rebuild(verts)`` builds the same tree on the device."""
+    ``scene.tris``.  ``Query(scene, refit=True, rebuild=True).rebuild(verts)`` builds the same tree on the device.
+    ``max_leaf`` > 1 (``srt_bvh_build_lbvh_leaf``, include/srt_rebuild_leaf.h) collapses every subtree of at most that
+    many triangles into one leaf, as ``Query.set_rebuild_leaf`` does on the device; ``nodes`` then holds 2m + 1 nodes."""
     import dataclasses
 
     if len(scene.bvhs) != 1:
@@ -384,8 +386,14 @@ def build_lbvh(scene: Scene, verts: np.ndarray | None = None) -> tuple["Scene", 
     verts = np.ascontiguousarray(verts).reshape(-1).copy()
     n = len(scene.tris)
     nodes, tris, order = np.zeros(max(2 * n - 1, 0), NODE_DTYPE), np.zeros(n, TRI_DTYPE), np.zeros(n, np.uint32)
-    check(lib().srt_bvh_build_lbvh(_ptr(scene.tris), n, _ptr(verts), len(verts), _ptr(nodes), _ptr(tris), _ptr(order)),
-          "srt_bvh_build_lbvh")
+    if max_leaf == 1:
+        check(lib().srt_bvh_build_lbvh(_ptr(scene.tris), n, _ptr(verts), len(verts), _ptr(nodes), _ptr(tris), _ptr(order)),
+              "srt_bvh_build_lbvh")
+    else:
+        n_nodes = C.c_uint32(0)
+        check(lib().srt_bvh_build_lbvh_leaf(_ptr(scene.tris), n, _ptr(verts), len(verts), int(max_leaf), _ptr(nodes),
+                                            C.byref(n_nodes), _ptr(tris), _ptr(order)), "srt_bvh_build_lbvh_leaf")
+        nodes = nodes[:n_nodes.value].copy()
     bvhs = scene.bvhs.copy()
     bvhs[0]["first_index"], bvhs[0]["count"] = 0, len(nodes)
     tri_input = None if scene.tri_input is None else scene.tri_input[order]

@@ -364,6 +364,14 @@ _REBUILD_SIGS = {
 }
 REBUILD_SYMBOLS = tuple(_REBUILD_SIGS)
 
+# include/srt_rebuild_leaf.h: leaves of several triangles for that rebuild (its own header and version)
+_REBUILD_LEAF_SIGS = {
+    "srt_rebuild_leaf_abi_version": (C.c_int, []),
+    "srt_query_set_rebuild_leaf": (C.c_int, [P, C.c_uint32]),
+    "srt_bvh_build_lbvh_leaf": (C.c_int, [P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.POINTER(C.c_uint32), P, P]),
+}
+REBUILD_LEAF_SYMBOLS = tuple(_REBUILD_LEAF_SIGS)
+
 _lib = None
 
 
@@ -399,7 +407,8 @@ def lib() -> C.CDLL:
                                   + list(_TEMPORAL_MOTION_SIGS.items()) + list(_VARIANCE_SIGS.items())
                                   + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
                                   + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
-                                  + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())):
+                                  + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())
+                                  + list(_REBUILD_LEAF_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -76,15 +76,18 @@ class Query(_Stage):
     ``refit=True`` (``SRT_QUERY_REFIT``, include/srt_refit.h) also uploads the vertex indices and a refit
     schedule, so :meth:`refit` can move the object to new vertex positions on the device.  ``rebuild=True`` (with
     ``refit=True``, one model; include/srt_rebuild.h) also allocates what :meth:`rebuild` needs to give the object a
-    new tree on the device.
+    new tree on the device; ``rebuild_leaf=n`` is :meth:`set_rebuild_leaf` at creation.
     """
 
     _prefix = "srt_query"
 
-    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False, rebuild: bool = False):
+    def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False, rebuild: bool = False,
+                 rebuild_leaf: int | None = None):
         super().__init__(device, stream)
         if rebuild and not refit:
             raise ValueError("rebuild=True needs refit=True (include/srt_rebuild.h)")
+        if rebuild_leaf is not None and not rebuild:
+            raise ValueError("rebuild_leaf needs rebuild=True (include/srt_rebuild_leaf.h)")
         s = scene
         args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
                 len(s.verts))
@@ -96,6 +99,8 @@ class Query(_Stage):
         if rebuild:
             try:
                 self.enable_rebuild()
+                if rebuild_leaf is not None:
+                    self.set_rebuild_leaf(rebuild_leaf)
             except Exception:
                 self.close()
                 raise
@@ -131,6 +136,14 @@ class Query(_Stage):
     def enable_rebuild(self):
         """``srt_query_enable_rebuild``: allocates what :meth:`rebuild` needs (``Query(..., rebuild=True)`` calls it)."""
         check(lib().srt_query_enable_rebuild(self.handle), "srt_query_enable_rebuild")
+
+    def set_rebuild_leaf(self, max_leaf: int):
+        """``srt_query_set_rebuild_leaf`` (include/srt_rebuild_leaf.h): from the next :meth:`rebuild` on, every subtree
+        of the linear BVH that covers at most ``max_leaf`` triangles (1..255; 1, the default, is one triangle a leaf)
+        becomes one leaf.  Enqueues nothing."""
+        if not 0 <= int(max_leaf) <= 0xFFFFFFFF:
+            raise ValueError("max_leaf must be in [1, 255]")
+        check(lib().srt_query_set_rebuild_leaf(self.handle, int(max_leaf)), "srt_query_set_rebuild_leaf")
 
     def rebuild(self, verts):
         """A new tree over the triangles at ``verts`` (``srt_query_rebuild``, include/srt_rebuild.h): a linear BVH

@@ -17,6 +17,12 @@ srt_amd.render.wave_vertices.  One JSON line per mesh:
   remap_ms          the hit remap of a rebuilt object per --rays hits: srt_query_closest on the rebuilt object minus the
                     same call on an object created from the host-built LBVH arrays (the same tree, no remap).
 
+With --leaf 1,2,4,8 (include/srt_rebuild_leaf.h) the tool measures the leaf collapse instead, one JSON line per mesh:
+per max_leaf the rebuild time as above, --repeat times over (the spread of those medians is the run-to-run noise), with
+the pairs, the depth and stack.in_hbm of the tree; and at the amplitudes of --waves the rate of srt_query_closest on the
+refit tree, the midpoint tree and the device LBVH of every max_leaf.  max_leaf 1 never calls the setting, so that column
+is the object a caller has without it.
+
 Nothing here is asserted: this is a measurement tool.
 """
 from __future__ import annotations
@@ -174,6 +180,82 @@ def run(args):
         pathlib.Path(args.out).write_text(json.dumps(doc, indent=1) + "\n")
 
 
+def run_leaf(args):
+    import torch
+
+    import srt_amd as S
+    from bench_queries import surface_rays
+    from bench_refit import closest_rate
+    from srt_amd import _lib
+    from srt_amd import render as R
+    from srt_amd.query import Query
+
+    def dev(a):
+        return torch.from_numpy(a.view(np.float32).reshape(-1, 8).copy()).cuda()
+
+    def tree(q):
+        return {"pairs": q.get_int("layout.pairs") // 64, "depth": q.get_int("rebuild.depth"), "stack_in_hbm": q.get_int("stack.in_hbm"),
+                "launches": q.get_int("rebuild.launches")}
+
+    results = []
+    for name in ("rubik", "knot"):
+        model = R.rubik_model(ROOT / "tests" / "golden" / "objects") if name == "rubik" else R.torus_knot_model()
+        scene = S.Scene.from_models([model])
+        verts = R.wave_vertices(scene.verts, args.wave)
+        vdev = dev(verts)
+        torch.cuda.synchronize()
+        r = {"mesh": name, "triangles": len(scene.tris), "vertices": len(verts), "wave": args.wave, "rebuild_batch": args.batch,
+             "rebuild": [], "rays": args.rays, "closest": [], "warmup": args.warmup, "reps": args.reps, "repeat": args.repeat}
+        for leaf in args.leaf:
+            runs = []
+            for _ in range(args.repeat):  # a fresh object each time: the spread of the medians is the noise
+                with Query(scene, refit=True, rebuild=True) as q:
+                    if leaf != 1:
+                        q.set_rebuild_leaf(leaf)
+                    (med, lo, hi), wall = time_rebuild(torch, q, vdev, len(verts), args.batch, args.warmup, args.reps)
+                    runs.append({"ms": round(med, 5), "ms_min_max": [round(lo, 5), round(hi, 5)], "wall_ms": round(wall, 5)})
+                    info = tree(q)
+            meds = [x["ms"] for x in runs]
+            r["rebuild"].append({"max_leaf": leaf, "rebuild_ms": round(statistics.median(meds), 5),
+                                 "rebuild_ms_runs": meds, "runs": runs, **info})
+        for amplitude in args.waves:
+            v = R.wave_vertices(scene.verts, amplitude)
+            refit = S.refit_scene(scene, v)
+            rays = dev(surface_rays(refit, args.rays))
+            vd = dev(v)
+            row = {"wave": amplitude, "lbvh": []}
+            with Query(scene, refit=True) as qr, Query(midpoint_scene(S, scene, v["pos"])) as qm:
+                qr.refit(vd)
+                for key, qq in (("refit", qr), ("midpoint", qm)):
+                    qq.set_bvh_count(1)
+                    med, lo, hi, _ = closest_rate(torch, qq, rays, args.warmup, args.reps)
+                    row[key] = {"ms": round(med, 4), "ms_min_max": [round(lo, 4), round(hi, 4)],
+                                "mrays_s": round(args.rays / med / 1e3, 1), "stack_in_hbm": qq.get_int("stack.in_hbm"),
+                                "pairs": qq.get_int("layout.pairs") // 64, "depth": qq.get_int("stack.entries") - 1}
+            for leaf in args.leaf:
+                with Query(scene, refit=True, rebuild=True) as ql:
+                    if leaf != 1:
+                        ql.set_rebuild_leaf(leaf)
+                    ql.rebuild(vd)
+                    ql.set_bvh_count(1)
+                    med, lo, hi, _ = closest_rate(torch, ql, rays, args.warmup, args.reps)
+                    row["lbvh"].append({"max_leaf": leaf, "ms": round(med, 4), "ms_min_max": [round(lo, 4), round(hi, 4)],
+                                        "mrays_s": round(args.rays / med / 1e3, 1),
+                                        "over_midpoint_rate": round(row["midpoint"]["ms"] / med, 3),
+                                        "over_refit_rate": round(row["refit"]["ms"] / med, 3), **tree(ql)})
+            r["closest"].append(row)
+        print(json.dumps(r), flush=True)
+        results.append(r)
+    if args.out:
+        doc = {"tool": "tools/bench_rebuild.py --leaf " + ",".join(str(x) for x in args.leaf), "device": torch.cuda.get_device_name(0),
+               "code_hash": _lib.lib().srt_code_hash().decode(),
+               "timing": "rebuild: torch.cuda.Event pair around a batch of srt_query_rebuild calls on the object's stream, per call "
+                         "(each call synchronises once); the median of --reps such batches, --repeat times over on fresh objects; "
+                         "closest: event pair around one enqueued srt_query_closest",
+               "meshes": results}
+        pathlib.Path(args.out).write_text(json.dumps(doc, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--wave", type=float, default=WAVE_AMPLITUDE)
@@ -183,12 +265,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", help="write the results to this JSON file")
+    ap.add_argument("--leaf", type=lambda t: [int(x) for x in t.split(",")], metavar="L,L,...",
+                    help="measure the leaf collapse at these max_leaf values (srt_rebuild_leaf.h) instead")
+    ap.add_argument("--waves", type=lambda t: [float(x) for x in t.split(",")], default=[0.25, 1.0, 4.0], metavar="A,A,...",
+                    help="with --leaf: the amplitudes the query rate is measured at")
+    ap.add_argument("--repeat", type=int, default=3, help="with --leaf: rebuild timings per max_leaf, each on a fresh object")
     args = ap.parse_args()
+    if args.leaf and (not all(1 <= x <= 255 for x in args.leaf) or args.repeat < 1):
+        ap.error("--leaf takes values in [1, 255], --repeat at least 1")
     if args.warmup < 3 or args.reps < 10 or args.batch < 1:
         ap.error("at least 3 warm-up rounds and 10 measured ones")
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
 
-    run(args)
+    (run_leaf if args.leaf else run)(args)
 
 
 if __name__ == "__main__":

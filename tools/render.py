@@ -2,7 +2,7 @@
 
 usage: python tools/render.py [--scene rubik|spheres|synthetic|torusknot|airplane_knot] [--width W] [--height H] [--spp N]
                               [--max-depth D] [--out frame.png] [--denoise] [--albedo] [--orbit K] [--spin DEG] [--variance]
-                              [--wave A [--orbit K [--albedo] [--rebuild-every K]]]
+                              [--wave A [--orbit K [--albedo] [--rebuild-every K [--rebuild-leaf L]]]]
 The output is image0 after N sampled frames (src/main.cpp:642-659 accumulation schedule),
 written top row first (PNG or PPM by extension).
 """
@@ -57,9 +57,14 @@ def main():
     ap.add_argument("--rebuild-every", type=int, default=0, metavar="K",
                     help="with --wave A --orbit N: every K-th frame the guide query gets a new tree, built on the device "
                          "(Query(scene, refit=True, rebuild=True).rebuild, include/srt_rebuild.h), and is refit otherwise")
+    ap.add_argument("--rebuild-leaf", type=int, default=None, metavar="L",
+                    help="with --rebuild-every K: those trees collapse every subtree of at most L triangles (1..255) into one "
+                         "leaf (Query.set_rebuild_leaf, include/srt_rebuild_leaf.h); the default is one triangle a leaf")
     a = ap.parse_args()
     if a.rebuild_every and (a.rebuild_every < 0 or not (a.wave and a.orbit)):
         ap.error("--rebuild-every K (K > 0) needs --wave A --orbit N")
+    if a.rebuild_leaf is not None and (not a.rebuild_every or not 1 <= a.rebuild_leaf <= 255):
+        ap.error("--rebuild-leaf L (1..255) needs --rebuild-every K")
     if a.wave and a.scene == "spheres":
         ap.error("--wave A needs a mesh scene")
     if a.wave and a.orbit and a.spin:
@@ -98,7 +103,7 @@ def main():
     if a.orbit:
         try:
             t0 = time.perf_counter()
-            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance, a.wave, a.albedo, a.rebuild_every)
+            paths = orbit(r, setup, a.orbit, a.spp, a.out, a.spin, a.variance, a.wave, a.albedo, a.rebuild_every, a.rebuild_leaf)
             dt = time.perf_counter() - t0
         finally:
             r.close()
@@ -183,7 +188,7 @@ def spin_frame(scene, degrees):
     return m.T.reshape(16).astype(np.float32)
 
 
-def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False, rebuild_every=0):
+def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo=False, rebuild_every=0, rebuild_leaf=None):
     """`frames` frames of `spp` samples, each after a reset of the accumulation: along ORBIT_STEP, or with `spin`
     (degrees per frame) under a still camera while the first model turns, or with `wave` (the amplitude) under a
     still camera while the wave's phase advances -- the per-frame calls of a deforming mesh, all on the device
@@ -209,7 +214,7 @@ def orbit(r, setup, frames, spp, out, spin=0.0, variance=False, wave=0.0, albedo
     cam, c = setup.camera, r.compute
     acc_ptr, _ = c.image_pointers()
     with Denoiser(setup.width, setup.height) as dn, Temporal(setup.width, setup.height) as tp, \
-            Query(setup.scene, refit=bool(wave), rebuild=bool(rebuild_every)) as q, \
+            Query(setup.scene, refit=bool(wave), rebuild=bool(rebuild_every), rebuild_leaf=rebuild_leaf) as q, \
             (Surface(setup.scene, refit=True) if albedo else contextlib.nullcontext()) as surf:
         q.set_bvh_count(setup.bvh_count)
         if wave:
