@@ -1,6 +1,6 @@
-// srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h, include/srt_rebuild.h and
-// include/srt_rebuild_leaf.h: srt::Query, RAII over the C ABI with the same method names, AssetUtils::RefitBVH and
-// AssetUtils::BuildLBVH.
+// srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h, include/srt_rebuild.h,
+// include/srt_rebuild_leaf.h and include/srt_rebuild_models.h: srt::Query, RAII over the C ABI with the same method names,
+// AssetUtils::RefitBVH, AssetUtils::BuildLBVH and AssetUtils::BuildLBVHModels.
 // Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
@@ -12,6 +12,7 @@
 #include "../srt_query.h"
 #include "../srt_rebuild.h"
 #include "../srt_rebuild_leaf.h"
+#include "../srt_rebuild_models.h"
 #include "../srt_refit.h"
 
 namespace srt {
@@ -55,6 +56,9 @@ class Query {
   void Rebuild(const srt_vertex* verts_dev, uint32_t n) { Check(srt_query_rebuild(q_, verts_dev, n), "srt_query_rebuild"); }
   // include/srt_rebuild_leaf.h: from the next Rebuild on, subtrees of at most `max_leaf` triangles (1..255) are leaves.
   void SetRebuildLeaf(uint32_t max_leaf) { Check(srt_query_set_rebuild_leaf(q_, max_leaf), "srt_query_set_rebuild_leaf"); }
+  // include/srt_rebuild_models.h: EnableRebuild for a scene of any number of BVH records; Rebuild then gives every record
+  // the tree of its own triangles.
+  void EnableRebuildModels() { Check(srt_query_enable_rebuild_models(q_), "srt_query_enable_rebuild_models"); }
   // Device pointers; both only enqueue on the query's stream.
   void closest(const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
     Check(srt_query_closest(q_, rays_dev, n, hits_dev), "srt_query_closest");
@@ -103,6 +107,20 @@ inline uint32_t BuildLBVH(const srt_triangle* tris, uint32_t n_tris, const srt_v
   if (int rc = srt_bvh_build_lbvh_leaf(tris, n_tris, verts, n_verts, max_leaf, nodes_out, &n_nodes, tris_out, order_out))
     throw std::runtime_error("srt_bvh_build_lbvh_leaf failed with status " + std::to_string(rc) + ": " + srt_last_error());
   return n_nodes;
+}
+
+// srt_bvh_build_lbvh_models: the host mirror of Query::Rebuild after EnableRebuildModels -- a block of nodes per BVH
+// record in record order (bvhs_out[r].first_index is its start), triangles and order sorted by (record, key); returns the
+// number of nodes written (nodes_out has room for 2 * n_tris - 1).
+inline uint32_t BuildLBVHModels(const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes, uint32_t n_nodes,
+                                const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts,
+                                uint32_t max_leaf, srt_bvh_record* bvhs_out, srt_bvh_node* nodes_out, srt_triangle* tris_out,
+                                uint32_t* order_out) {
+  uint32_t n_out = 0;
+  if (int rc = srt_bvh_build_lbvh_models(bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, max_leaf, bvhs_out,
+                                         nodes_out, &n_out, tris_out, order_out))
+    throw std::runtime_error("srt_bvh_build_lbvh_models failed with status " + std::to_string(rc) + ": " + srt_last_error());
+  return n_out;
 }
 
 }  // namespace AssetUtils

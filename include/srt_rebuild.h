@@ -29,7 +29,7 @@
  * n == 1 keeps a leaf root (the rebuild reduces to a refit); n == 2 is one pair of leaves.
  *
  * Out of scope: SAH (leaves of several triangles by collapsing subtrees: srt_rebuild_leaf.h); a changing n_verts or
- * triangle list.
+ * triangle list.  Scenes of more than one BVH record: srt_rebuild_models.h, whose enable call takes them.
  *
  * Additive to srt_amd.h, srt_query.h and srt_refit.h (their ABI versions are unchanged); versioned on its own.
  */

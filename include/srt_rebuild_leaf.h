@@ -22,7 +22,8 @@
  * Depth and heights only shrink against max_leaf == 1; 255 keeps PlanStack's 2-dword packing (leaf counts below
  * 256); max_leaf == 1 is srt_rebuild.h's tree exactly.
  *
- * Out of scope: SAH or any split other than Karras'; scenes of more than one BVH record.
+ * Out of scope: SAH or any split other than Karras'.  Scenes of more than one BVH record: srt_rebuild_models.h, where
+ * this header's max_leaf applies to every record.
  *
  * Additive to srt_rebuild.h and the headers under it (their ABI versions are unchanged); versioned on its own.
  */

@@ -262,6 +262,15 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   else if (n == "rebuild.max_leaf") *v = q->rebuild ? (int)q->rebuild->largest_leaf : 0;
   else if (n == "rebuild.pairs") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->pairs) : 0;
   else if (n == "rebuild.leaf_bytes") *v = q->rebuild ? srt::stage::SaturateInt(q->rebuild->leaf_bytes) : 0;
+  else if (n.rfind("rebuild.height.", 0) == 0) {  // pairs at one height of the last rebuild's tree, as the device counted
+    char* end = nullptr;
+    const unsigned long h = std::strtoul(name + 15, &end, 10);
+    if (end == name + 15 || *end != '\0') return SRT_ERR_NOT_FOUND;
+    *v = q->rebuild && q->rebuild->count > 0 && h < (unsigned long)srt::rebuild::kHeightBins
+             ? srt::stage::SaturateInt(q->rebuild->summary[h]) : 0;
+  }
+  else if (n == "rebuild.models") *v = q->rebuild && q->rebuild->models ? 1 : 0;
+  else if (n == "rebuild.records") *v = q->rebuild ? (int)q->rebuild->records : 0;
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }

@@ -43,6 +43,14 @@ struct State {
   size_t scan_temp_bytes = 0, leaf_bytes = 0;
   uint32_t leaf_summary[2] = {};     // what the last collapsed rebuild read back from d_leafsum
   uint32_t pairs = 0, largest_leaf = 0;  // of the last rebuild's tree
+  // srt_query_enable_rebuild_models (include/srt_rebuild_models.h); the arrays only with two records or more, where
+  // d_keys_in stays null (the sort's input is d_keys64_in) and d_box too (the boxes follow the arrival words in d_zeroed)
+  bool models = false;
+  uint32_t records = 1;
+  Segments segments;                         // s_r, n_r: fixed when enabled
+  stage::DevPtr<uint32_t> d_owner, d_pos_rec;  // n each: creation index -> record, position -> record
+  stage::DevPtr<uint2> d_seg;                  // per record
+  stage::DevPtr<uint64_t> d_keys64_in, d_keys64;
 };
 
 }  // namespace rebuild

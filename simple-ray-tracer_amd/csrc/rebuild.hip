@@ -1,8 +1,9 @@
 // rebuild.hip -- the device rebuild of include/srt_rebuild.h: the rebuild data of a query object, the launches of
 // rebuild.hpp's kernels around hipcub's radix sort, the one readback, the new schedule and stack plan, the
 // refit that fills the boxes, and the hit remap; and include/srt_rebuild_leaf.h's max_leaf, which puts a range kernel,
-// hipcub's scan and an emit kernel in the hierarchy kernel's place.  A translation unit of its own beside query.hip
-// and refit.hip.
+// hipcub's scan and an emit kernel in the hierarchy kernel's place; and include/srt_rebuild_models.h's rebuild of several
+// BVH records at once (EnableModels, RebuildModels: segment bounds, a 64-bit sort).  A translation unit of its own beside
+// query.hip and refit.hip.
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
 #include <hipcub/device/device_scan.hpp>
@@ -14,6 +15,7 @@
 
 #include "../../include/srt_rebuild.h"
 #include "../../include/srt_rebuild_leaf.h"
+#include "../../include/srt_rebuild_models.h"
 #include "query_object.hpp"
 #include "rebuild.hpp"
 #include "rebuild_host.hpp"
@@ -36,6 +38,53 @@ hipError_t Sort(State& st, uint32_t n, hipStream_t stream, void* temp, size_t& t
 // rank = the exclusive sum of the n survival flags (the last is 0, so rank[n - 1] is the number of survivors)
 hipError_t Scan(const uint32_t* flags, uint32_t* rank, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
   return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, flags, rank, (int)n, stream);
+}
+
+// The end of every rebuild, after its one synchronisation: the schedule from the counts per height, the object's
+// description of the tree built (m pairs in the first `extent` slots of the pair array), the stack plan, the refit.
+int Adopt(srt_query* q, const srt_vertex* verts_dev, int launches, uint32_t m, uint32_t extent, uint32_t largest,
+          bool summary_valid) {
+  State& st = *q->rebuild;
+  const uint32_t n = q->n_tris;
+  hipStream_t s = q->stream;
+  refit::Schedule sched;
+  if (!summary_valid || !ScheduleFromCounts(st.summary, kHeightBins, m, &sched)) {
+    srt::SetError("srt_query_rebuild: the device hierarchy is not a tree over every triangle (non-finite vertices?)");
+    return SRT_ERR_STATE;
+  }
+  st.summary[kHeightBins] = sched.heights;
+  st.summary[kHeightBins + 1] = m;
+  // the object describes the tree built: the first `extent` pairs of the array's n - 1
+  const size_t pb = 4 * sizeof(float4) * (size_t)(extent ? extent : 1u), tb = sizeof(uint4) * (size_t)n;
+  q->scene_bytes = q->scene_bytes - q->pairs_bytes + pb;
+  q->pairs_bytes = pb;
+  q->n_pairs = m;
+  q->refit_bytes = tb + sizeof(uint32_t) * ((size_t)m + kHeightBins + 1);
+  st.tail_first.assign(sched.first.begin() + sched.tail_begin, sched.first.end());
+  STAGE_HIP_OK(hipMemcpyAsync(q->d_schedule + m, st.tail_first.data(), sizeof(uint32_t) * st.tail_first.size(),
+                              hipMemcpyHostToDevice, s));
+  q->schedule = std::move(sched);
+  // the stack plan of the new tree: its largest leaf, depth == heights
+  query::Layout shape;
+  shape.n_pairs = extent;
+  shape.max_leaf = largest;
+  shape.depth = (int)q->schedule.heights;
+  const query::StackPlan plan = query::PlanStack(shape, n);
+  const query::StackPlan old = q->plan;
+  q->plan = plan;
+  if (plan.in_hbm != old.in_hbm || plan.packed != old.packed || plan.lds_bytes != old.lds_bytes)
+    if (int rc = query::PlanGrid(q)) return rc;
+  if (plan.hbm_block_bytes != old.hbm_block_bytes) {  // the next query allocates the area it needs
+    q->d_stack.Free();
+    q->stack_blocks = 0;
+  }
+  if (int rc = refit::Enqueue(q, verts_dev)) return rc;
+  st.launches = launches + (int)q->schedule.launches;
+  st.depth = shape.depth;
+  st.pairs = m;
+  st.largest_leaf = largest;
+  ++st.count;
+  return SRT_OK;
 }
 
 }  // namespace
@@ -206,45 +255,185 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   }
   const uint32_t m = leaf_root ? 0u : (collapse ? st.leaf_summary[0] : n_pairs);
   const uint32_t largest = leaf_root ? n : (collapse ? st.leaf_summary[1] : 1u);
-  refit::Schedule sched;
-  if ((collapse && !leaf_root && !LeafSummaryValid(m, largest, n, max_leaf)) ||
-      !ScheduleFromCounts(st.summary, kHeightBins, m, &sched)) {
-    srt::SetError("srt_query_rebuild: the device hierarchy is not a tree over every triangle (non-finite vertices?)");
-    return SRT_ERR_STATE;
+  return Adopt(q, verts_dev, launches, m, m, largest, !collapse || leaf_root || LeafSummaryValid(m, largest, n, max_leaf));
+}
+
+// -- include/srt_rebuild_models.h -----------------------------------------------------------------------------------------
+namespace {
+
+// The (record, key) sort: bits [0, 32 + the records' bits) of the 64-bit keys; stable, as every radix sort is.
+int RecordBits(uint32_t records) {
+  int bits = 1;
+  while (bits < 32 && (1ull << bits) < records) ++bits;
+  return bits;
+}
+
+hipError_t SortModels(State& st, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
+  return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint64_t*)st.d_keys64_in.get(), st.d_keys64.get(),
+                                            (const uint32_t*)st.d_vals_in.get(), st.d_order.get(), n, 0,
+                                            32 + RecordBits(st.records), stream);
+}
+
+size_t ZeroedWords(uint32_t n, uint32_t records) { return 2 * (size_t)kHeightBins + (n - 1) + 8 * (size_t)records; }
+
+}  // namespace
+
+// Two records or more (one record is Enable above, unchanged): the owners from the object's own pairs and roots, then
+// Enable's allocations with 64-bit sort keys, the per-record boxes behind the arrival words, and the segment arrays.
+int EnableModels(srt_query* q) {
+  STAGE_HIP_OK(hipSetDevice(q->device));
+  const uint32_t n = q->n_tris, n_pairs = n - 1, records = q->n_bvhs;
+  STAGE_HIP_OK(hipStreamSynchronize(q->stream));
+  std::vector<query::F4> pairs(q->pairs_bytes / sizeof(query::F4)), roots(q->roots_bytes / sizeof(query::F4));
+  STAGE_HIP_OK(hipMemcpy(pairs.data(), q->d_pairs, q->pairs_bytes, hipMemcpyDeviceToHost));
+  STAGE_HIP_OK(hipMemcpy(roots.data(), q->d_roots, q->roots_bytes, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> owner(n);
+  std::string err;
+  if (roots.size() < 2 * ((size_t)records + 1) || pairs.size() < 4 * (size_t)q->n_pairs) return SRT_ERR_STATE;
+  if (int rc = OwnersFromLayout(pairs.data(), q->n_pairs, roots.data(), records, n, owner.data(), &err)) {
+    srt::SetError(err);
+    return rc;
   }
-  st.summary[kHeightBins] = sched.heights;
-  st.summary[kHeightBins + 1] = m;
-  // the object describes the tree built: the first m pairs of the array's n - 1
-  const size_t pb = 4 * sizeof(float4) * (size_t)(m ? m : 1u), tb = sizeof(uint4) * (size_t)n;
-  q->scene_bytes = q->scene_bytes - q->pairs_bytes + pb;
-  q->pairs_bytes = pb;
-  q->n_pairs = m;
-  q->refit_bytes = tb + sizeof(uint32_t) * ((size_t)m + kHeightBins + 1);
-  st.tail_first.assign(sched.first.begin() + sched.tail_begin, sched.first.end());
-  STAGE_HIP_OK(hipMemcpyAsync(q->d_schedule + m, st.tail_first.data(), sizeof(uint32_t) * st.tail_first.size(),
-                              hipMemcpyHostToDevice, s));
-  q->schedule = std::move(sched);
-  // the stack plan of the new tree: its largest leaf, depth == heights
-  query::Layout shape;
-  shape.n_pairs = m;
-  shape.max_leaf = largest;
-  shape.depth = (int)q->schedule.heights;
-  const query::StackPlan plan = query::PlanStack(shape, n);
-  const query::StackPlan old = q->plan;
-  q->plan = plan;
-  if (plan.in_hbm != old.in_hbm || plan.packed != old.packed || plan.lds_bytes != old.lds_bytes)
-    if (int rc = query::PlanGrid(q)) return rc;
-  if (plan.hbm_block_bytes != old.hbm_block_bytes) {  // the next query allocates the area it needs
-    q->d_stack.Free();
-    q->stack_blocks = 0;
+  std::unique_ptr<State> st(new State());
+  st->models = true;
+  st->records = records;
+  st->segments = SegmentsOf(owner.data(), n, records);
+  if (int rc = CheckSegments(st->segments, &err)) {
+    srt::SetError(err);
+    return rc;
   }
-  if (int rc = refit::Enqueue(q, verts_dev)) return rc;
-  st.launches = launches + (int)q->schedule.launches;
-  st.depth = shape.depth;
-  st.pairs = m;
-  st.largest_leaf = largest;
-  ++st.count;
+  std::vector<uint32_t> pos_rec(n);
+  std::vector<uint2> seg(records);
+  for (uint32_t r = 0; r < records; ++r) {
+    seg[r] = make_uint2(st->segments.first[r], st->segments.count[r]);
+    for (uint32_t k = 0; k < st->segments.count[r]; ++k) pos_rec[st->segments.first[r] + k] = r;
+  }
+  const size_t pair_bytes = 4 * sizeof(float4) * (size_t)n_pairs;
+  const size_t sched = sizeof(uint32_t) * ((size_t)n_pairs + kHeightBins + 1);
+  const size_t per_tri = sizeof(uint32_t) * (size_t)n;
+  const size_t zeroed = sizeof(uint32_t) * ZeroedWords(n, records);
+  const size_t seg_bytes = sizeof(uint2) * (size_t)records;
+  STAGE_HIP_OK(st->d_pairs.Alloc(pair_bytes));
+  STAGE_HIP_OK(st->d_triples.Alloc(sizeof(uint4) * (size_t)n));
+  STAGE_HIP_OK(st->d_schedule.Alloc(sched));
+  STAGE_HIP_OK(st->d_keys64_in.Alloc(2 * per_tri));
+  STAGE_HIP_OK(st->d_keys64.Alloc(2 * per_tri));
+  STAGE_HIP_OK(st->d_vals_in.Alloc(per_tri));
+  STAGE_HIP_OK(st->d_keys.Alloc(per_tri));
+  STAGE_HIP_OK(st->d_order.Alloc(per_tri));
+  STAGE_HIP_OK(st->d_parent.Alloc(sizeof(uint32_t) * (2 * (size_t)n)));
+  STAGE_HIP_OK(st->d_height.Alloc(sizeof(uint32_t) * (size_t)n_pairs));
+  STAGE_HIP_OK(st->d_zeroed.Alloc(zeroed));
+  STAGE_HIP_OK(st->d_owner.Alloc(per_tri));
+  STAGE_HIP_OK(st->d_pos_rec.Alloc(per_tri));
+  STAGE_HIP_OK(st->d_seg.Alloc(seg_bytes));
+  size_t temp = 0;
+  STAGE_HIP_OK(SortModels(*st, n, q->stream, nullptr, temp));  // the size only
+  st->temp_bytes = temp ? temp : 16;
+  STAGE_HIP_OK(st->d_temp.Alloc(st->temp_bytes));
+  STAGE_HIP_OK(hipMemcpyAsync(st->d_owner, owner.data(), per_tri, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(st->d_pos_rec, pos_rec.data(), per_tri, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemcpyAsync(st->d_seg, seg.data(), seg_bytes, hipMemcpyHostToDevice, q->stream));
+  STAGE_HIP_OK(hipMemsetAsync(st->d_order, 0, per_tri, q->stream));
+  STAGE_HIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
+  st->bytes = pair_bytes + sizeof(uint4) * (size_t)n + sched + 4 * per_tri + 3 * per_tri + sizeof(uint32_t) * (2 * (size_t)n) +
+              sizeof(uint32_t) * (size_t)n_pairs + zeroed + 2 * per_tri + seg_bytes + st->temp_bytes;
+  q->rebuild = std::move(st);
   return SRT_OK;
+}
+
+int RebuildModels(srt_query* q, const srt_vertex* verts_dev) {
+  STAGE_HIP_OK(hipSetDevice(q->device));
+  State& st = *q->rebuild;
+  const uint32_t n = q->n_tris;         // >= 2: two records or more, a triangle each at least
+  const uint32_t n_pairs = n - 1;       // the pair array's capacity
+  const uint32_t max_leaf = st.max_leaf;
+  const bool collapse = max_leaf > 1;
+  uint32_t karras_pairs = 0, root_leaf = 0;  // what the segments say before the device ran
+  SegmentShape(st.segments, max_leaf, &karras_pairs, &root_leaf);
+  const bool first_time = st.count == 0;
+  if (first_time) {
+    std::swap(st.d_pairs, q->d_pairs);
+    std::swap(st.d_triples, q->d_triples);
+    std::swap(st.d_schedule, q->d_schedule);
+  }
+  BParams bp;
+  std::memset(&bp, 0, sizeof bp);
+  bp.pairs = q->d_pairs;
+  bp.roots = q->d_roots;
+  bp.triples0 = st.d_triples;
+  bp.triples = q->d_triples;
+  bp.verts = reinterpret_cast<const float4*>(verts_dev);
+  bp.vals_in = st.d_vals_in;
+  bp.keys = st.d_keys;
+  bp.keys_out = st.d_keys;
+  bp.order = st.d_order;
+  bp.parent = st.d_parent;
+  bp.counts = st.d_zeroed;
+  bp.cursor = st.d_zeroed + kHeightBins;
+  bp.arrive = st.d_zeroed + 2 * kHeightBins;
+  bp.seg_box = st.d_zeroed + 2 * kHeightBins + n_pairs;
+  bp.height = st.d_height;
+  bp.schedule = q->d_schedule;
+  bp.n_verts = q->n_verts;
+  bp.n_tris = n;
+  bp.owner = st.d_owner;
+  bp.pos_rec = st.d_pos_rec;
+  bp.seg = st.d_seg;
+  bp.keys64_in = st.d_keys64_in;
+  bp.keys64 = st.d_keys64;
+  bp.n_records = st.records;
+  if (collapse) {
+    bp.split = st.d_split;
+    bp.flags = st.d_flags;
+    bp.rank = st.d_rank;
+    bp.leafsum = st.d_leafsum;
+    bp.max_leaf = max_leaf;
+  }
+  hipStream_t s = q->stream;
+  int launches = 0;
+#define REBUILD_LAUNCH(kernel, blocks)                                            \
+  do {                                                                            \
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, bp);             \
+    STAGE_HIP_OK(hipGetLastError());                                              \
+    ++launches;                                                                   \
+  } while (0)
+  STAGE_HIP_OK(hipMemsetAsync(st.d_zeroed, 0, sizeof(uint32_t) * ZeroedWords(n, st.records), s));
+  REBUILD_LAUNCH(seg_box_kernel, Blocks(n));
+  REBUILD_LAUNCH(keys_models_kernel, Blocks(n));
+  size_t temp = st.temp_bytes;
+  STAGE_HIP_OK(SortModels(st, n, s, st.d_temp, temp));
+  ++launches;  // (counted as one, as the one-record sort is)
+  REBUILD_LAUNCH(permute_models_kernel, Blocks(n));
+  if (collapse) {
+    REBUILD_LAUNCH(range_models_kernel, Blocks(n));
+    size_t scan_temp = st.scan_temp_bytes;
+    STAGE_HIP_OK(Scan(st.d_flags, st.d_rank, n, s, st.d_scan_temp, scan_temp));
+    ++launches;
+    REBUILD_LAUNCH(emit_models_kernel, Blocks(n));
+    REBUILD_LAUNCH((climb_kernel<true, true>), Blocks(n));
+    REBUILD_LAUNCH((schedule_kernel<true, true>), Blocks(n_pairs));
+    if (karras_pairs == 0)  // every record a leaf root: pair 0, which srt_query_copy_layout still copies, keeps nothing
+      STAGE_HIP_OK(hipMemsetAsync(q->d_pairs, 0, 4 * sizeof(float4), s));
+  } else {
+    REBUILD_LAUNCH(karras_models_kernel, Blocks(n));
+    REBUILD_LAUNCH((climb_kernel<false, true>), Blocks(n));
+    REBUILD_LAUNCH((schedule_kernel<false, true>), Blocks(n_pairs));
+  }
+#undef REBUILD_LAUNCH
+  STAGE_HIP_OK(hipMemcpyAsync(st.summary, st.d_zeroed, sizeof(uint32_t) * kHeightBins, hipMemcpyDeviceToHost, s));
+  if (collapse)
+    STAGE_HIP_OK(hipMemcpyAsync(st.leaf_summary, st.d_leafsum, sizeof st.leaf_summary, hipMemcpyDeviceToHost, s));
+  STAGE_HIP_OK(hipStreamSynchronize(s));  // the one synchronisation
+  if (first_time) {
+    st.d_pairs.Free();
+    st.d_schedule.Free();
+  }
+  const uint32_t m = collapse ? st.leaf_summary[0] : karras_pairs;
+  const uint32_t device_largest = collapse ? st.leaf_summary[1] : (karras_pairs ? 1u : 0u);
+  const uint32_t largest = device_largest > root_leaf ? device_largest : root_leaf;
+  const bool valid = !collapse || ModelsSummaryValid(m, device_largest, karras_pairs, max_leaf);
+  return Adopt(q, verts_dev, launches, m, collapse ? m : n_pairs, largest, valid);
 }
 
 int EnqueueRemap(srt_query* q, srt_hit* hits_dev, uint32_t n) {
@@ -309,7 +498,35 @@ int srt_query_rebuild(srt_query* q, const srt_vertex* verts_dev, uint32_t n_vert
     srt::SetError(err);
     return rc;
   }
+  if (q->rebuild->models && q->rebuild->records > 1) return srt::rebuild::RebuildModels(q, verts_dev);
   return srt::rebuild::Rebuild(q, verts_dev);
+}
+
+int srt_rebuild_models_abi_version(void) { return SRT_REBUILD_MODELS_ABI_VERSION; }
+
+int srt_bvh_build_lbvh_models(const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_node* nodes, uint32_t n_nodes,
+                              const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts,
+                              uint32_t max_leaf, srt_bvh_record* bvhs_out, srt_bvh_node* nodes_out, uint32_t* n_nodes_out,
+                              srt_triangle* tris_out, uint32_t* order_out) {
+  std::string err;
+  const int rc = srt::rebuild::BuildLBVHModels(bvhs, n_bvhs, nodes, n_nodes, tris, n_tris, verts, n_verts, max_leaf, bvhs_out,
+                                               nodes_out, n_nodes_out, tris_out, order_out, &err);
+  if (rc) srt::SetError(err);
+  return rc;
+}
+
+int srt_query_enable_rebuild_models(srt_query* q) {
+  std::string err;
+  if (int rc = srt::rebuild::CheckEnableModels(q != nullptr, q && q->refit, q ? q->first_index0 : 0, q ? q->n_tris : 0, &err)) {
+    srt::SetError(err);
+    return rc;
+  }
+  if (q->rebuild) return SRT_OK;
+  if (q->n_bvhs > 1) return srt::rebuild::EnableModels(q);
+  // one record owns every triangle its root reaches, and the layout holds no other: srt_rebuild.h's object exactly
+  if (int rc = srt::rebuild::Enable(q)) return rc;
+  q->rebuild->models = true;
+  return SRT_OK;
 }
 
 int srt_query_tri_order(srt_query* q, uint32_t* order_host, uint32_t n) {

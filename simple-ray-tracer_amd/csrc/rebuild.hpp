@@ -66,6 +66,16 @@ struct BParams {
   const uint32_t* rank;     // n: the exclusive sum of flags; rank[n - 1] == m
   uint32_t* leafsum;        // m, the largest leaf count
   uint32_t max_leaf;
+  // include/srt_rebuild_models.h, two records or more only (null / 0 otherwise); `keys` is then what permute_models_kernel
+  // unpacked, and pair indices are global: record r's Karras node k is pair s_r + k
+  const uint32_t* owner;    // n: creation index -> record
+  const uint32_t* pos_rec;  // n: position -> record (the segments never move)
+  const uint2* seg;         // per record: s_r, n_r
+  uint32_t* seg_box;        // 8 per record: ~ordered(lo) xyz, -, ordered(hi) xyz, -; zero at launch, atomic max
+  uint64_t* keys64_in;      // creation order: (record << 32) | morton
+  const uint64_t* keys64;   // sorted
+  uint32_t* keys_out;       // sorted: the low dwords (what `keys` points to)
+  uint32_t n_records;
 };
 
 constexpr uint32_t kNoOwner = 0xFFFFFFFFu;  // (not below any pair count: such a position starts no climb)
@@ -227,7 +237,9 @@ __device__ __forceinline__ uint32_t pair_count(const BParams& bp) {
   return m < bp.n_tris - 1u ? m : bp.n_tris - 1u;
 }
 
-template <bool LEAF>
+// SEG (include/srt_rebuild_models.h): the climb ends at a pair without a parent -- a record's root, whose parent word
+// is kNoOwner -- not at pair 0.
+template <bool LEAF, bool SEG = false>
 __global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
   __shared__ uint32_t bins[kHeightBins];
   if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
@@ -245,7 +257,7 @@ __global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
       h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;  // (the depth bound keeps it below)
       bp.height[p] = h;
       atomicAdd(&bins[h], 1u);
-      if (p == 0u) break;  // the root
+      if (!SEG && p == 0u) break;  // the root
       val = h + 1u;
       p = bp.parent[p];
     }
@@ -254,7 +266,9 @@ __global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
   if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) atomicAdd(bp.counts + threadIdx.x, bins[threadIdx.x]);
 }
 
-template <bool LEAF>
+// SEG without LEAF: the pair array has unused slots (index e_r of every record); a pair exists iff both its children
+// arrived, which left its arrival word non-zero.
+template <bool LEAF, bool SEG = false>
 __global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
   __shared__ uint32_t bins[kHeightBins], base[kHeightBins];
   if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
@@ -262,7 +276,8 @@ __global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
   const uint32_t n_pairs = pair_count<LEAF>(bp);
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   uint32_t h = 0u, rank = 0u;
-  if (p < n_pairs) {
+  const bool exists = p < n_pairs && (LEAF || !SEG || bp.arrive[p] != 0u);
+  if (exists) {
     h = bp.height[p];
     h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;
     rank = atomicAdd(&bins[h], 1u);
@@ -274,7 +289,7 @@ __global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
     base[threadIdx.x] = first + atomicAdd(bp.cursor + threadIdx.x, bins[threadIdx.x]);
   }
   __syncthreads();
-  if (p < n_pairs) {
+  if (exists) {
     const uint32_t at = base[h] + rank;
     if (at < n_pairs) bp.schedule[at] = p;
   }
@@ -352,6 +367,183 @@ __global__ __launch_bounds__(256) void root_leaf_kernel(BParams bp) {
     bp.roots[2 * r] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
     bp.roots[2 * r + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(bp.n_tris));
   }
+}
+
+// -- two records or more (include/srt_rebuild_models.h) -------------------------------------------------------------------
+// seg_box_kernel: one lane per triangle; the box of its owner.  Floats go through the order-preserving map to uint32, the
+//   lower bounds complemented, so every bound is an atomic max over words zeroed at launch: min and max of values are
+//   exact and commute, no neutral element and no infinity is needed, and a record's box holds its own triangles only.  A
+//   block whose triangles all have one owner folds in the block first and issues six atomics.
+// keys_models_kernel: the key in the owner's box, the owner in the high dword.
+// permute_models_kernel: permute_kernel, and the sorted keys' low dwords for the hierarchy.
+// karras_models_kernel / range_models_kernel / emit_models_kernel: one lane per position; its segment from pos_rec and
+//   seg, the node by SegmentSplit, and the root record of the segment (and the ghost root for record 0) by the lane of the
+//   segment's first position.  A root pair's parent word is kNoOwner.
+__device__ __forceinline__ uint32_t ordered(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float unordered(uint32_t e) {
+  return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e);
+}
+
+__device__ __forceinline__ uint32_t owner_of(const BParams& bp, uint32_t t) {
+  const uint32_t r = bp.owner[t];
+  return r < bp.n_records ? r : bp.n_records - 1u;
+}
+
+__global__ __launch_bounds__(256) void seg_box_kernel(BParams bp) {
+  __shared__ uint32_t first_owner;
+  const uint32_t t0 = blockIdx.x * kBlock;  // (< n_tris: the grid is ceil(n / 256) blocks)
+  const uint32_t t = t0 + threadIdx.x;
+  const bool have = t < bp.n_tris;
+  const uint32_t r = owner_of(bp, have ? t : t0);
+  if (threadIdx.x == 0) first_owner = r;
+  __syncthreads();
+  const uint32_t r0 = first_owner;
+  const bool one_owner = __syncthreads_and(r == r0) != 0;  // block-uniform
+  Span3 s = tri_span(bp, have ? t : t0);
+  bool store = have;
+  if (one_owner) {
+    s = block_span(s, have, tri_span(bp, t0));
+    store = threadIdx.x == 0;
+  }
+  if (store) {
+    uint32_t* o = bp.seg_box + 8 * (size_t)r;
+    for (int k = 0; k < 3; ++k) {
+      atomicMax(o + k, ~ordered(s.lo[k]));
+      atomicMax(o + 4 + k, ordered(s.hi[k]));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void keys_models_kernel(BParams bp) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= bp.n_tris) return;
+  const uint32_t r = owner_of(bp, t);
+  const uint32_t* box = bp.seg_box + 8 * (size_t)r;
+  const Span3 s = tri_span(bp, t);
+  uint32_t q[3];
+  for (int k = 0; k < 3; ++k) q[k] = Cell(unordered(~box[k]), unordered(box[4 + k]), s.lo[k], s.hi[k]);
+  bp.keys64_in[t] = RecordKey(r, Morton(q[0], q[1], q[2]));
+  bp.vals_in[t] = t;
+}
+
+__global__ __launch_bounds__(256) void permute_models_kernel(BParams bp) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= bp.n_tris) return;
+  bp.keys_out[p] = (uint32_t)bp.keys64[p];
+  const uint32_t src = bp.order[p];
+  bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];
+}
+
+// The segment of position i (< n): s <= i < s + c <= n whatever the device arrays hold.
+struct Segment {
+  uint32_t r, s, c;
+};
+
+__device__ __forceinline__ Segment segment_of(const BParams& bp, uint32_t i) {
+  Segment g;
+  g.r = bp.pos_rec[i];
+  g.r = g.r < bp.n_records ? g.r : bp.n_records - 1u;
+  const uint2 sc = bp.seg[g.r];
+  g.s = sc.x <= i ? sc.x : i;
+  g.c = sc.y <= bp.n_tris - g.s ? sc.y : bp.n_tris - g.s;
+  g.c = i - g.s < g.c ? g.c : i - g.s + 1u;
+  return g;
+}
+
+// Root record r, and the ghost root (record n_records) beside record 0: `ref` is a pair index (count 0) or a position.
+__device__ __forceinline__ void put_root(const BParams& bp, uint32_t r, uint32_t ref, uint32_t count) {
+  for (uint32_t at = r;; at = bp.n_records) {
+    bp.roots[2 * (size_t)at] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(ref));
+    bp.roots[2 * (size_t)at + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(count));
+    if (r != 0u || at == bp.n_records) break;
+  }
+}
+
+__global__ __launch_bounds__(256) void karras_models_kernel(BParams bp) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;  // >= 2
+  if (i >= n) return;
+  const Segment g = segment_of(bp, i);
+  if (i == g.s) {
+    const Slot root = SegmentRoot(g.s, g.c, 1u);
+    put_root(bp, g.r, root.index, root.count);
+    if (root.count == 0u) bp.parent[i < n - 1u ? i : n - 2u] = kNoOwner;  // (c >= 2: i <= n - 2)
+    else bp.parent[n - 1u + i] = kNoOwner;                                // a leaf root: its position starts no climb
+  }
+  if (i + 1u >= n) return;  // (no pair slot n - 1)
+  float4* rec = bp.pairs + 4 * (size_t)i;
+  if (i - g.s + 1u >= g.c) {  // index e_r: unused, kept zero
+    for (int k = 0; k < 4; ++k) rec[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  const Split sp = SegmentSplit(bp.keys, g.s, g.c, i);
+  const Child l{(uint32_t)sp.gamma, sp.first == sp.gamma}, r{(uint32_t)(sp.gamma + 1), sp.last == sp.gamma + 1};
+  put_child(rec, l);
+  put_child(rec + 2, r);
+  const uint32_t li = l.leaf ? n - 1 + (l.index < n ? l.index : n - 1) : (l.index < n - 1 ? l.index : n - 2);
+  const uint32_t ri = r.leaf ? n - 1 + (r.index < n ? r.index : n - 1) : (r.index < n - 1 ? r.index : n - 2);
+  bp.parent[li] = i;
+  bp.parent[ri] = i;
+}
+
+__global__ __launch_bounds__(256) void range_models_kernel(BParams bp) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;  // >= 2
+  if (i >= n) return;
+  if (i == 0) bp.leafsum[1] = 0u;
+  bp.parent[n - 1 + i] = kNoOwner;
+  const Segment g = segment_of(bp, i);
+  uint4 out = make_uint4(0u, 0u, 0u, 0u);
+  if (g.c > bp.max_leaf && i - g.s + 1u < g.c) {
+    const Split sp = SegmentSplit(bp.keys, g.s, g.c, i);
+    out = make_uint4((uint32_t)sp.first, (uint32_t)sp.last, (uint32_t)sp.gamma, Survives(sp, bp.max_leaf) ? 1u : 0u);
+  }
+  if (i + 1u < n) bp.split[i] = out;
+  bp.flags[i] = out.w;
+}
+
+__global__ __launch_bounds__(256) void emit_models_kernel(BParams bp) {
+  __shared__ uint32_t largest;
+  if (threadIdx.x == 0) largest = 0u;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t n = bp.n_tris;
+  if (i == 0) bp.leafsum[0] = bp.rank[n - 1u];
+  if (i < n) {
+    const Segment g = segment_of(bp, i);
+    if (i == g.s) {
+      const Slot root = SegmentRoot(g.s, g.c, bp.max_leaf);
+      if (root.count > 0u) {
+        put_root(bp, g.r, root.index, root.count);
+      } else {  // node s_r survives: c > max_leaf
+        uint32_t rr = bp.rank[i < n - 1u ? i : n - 2u];
+        rr = rr < n - 1u ? rr : n - 2u;
+        put_root(bp, g.r, rr, 0u);
+        bp.parent[rr] = kNoOwner;
+      }
+    }
+  }
+  if (i + 1 < n) {
+    const uint4 sp4 = bp.split[i];
+    if (sp4.w != 0u) {
+      Split sp;
+      sp.first = sp4.x;
+      sp.last = sp4.y;
+      sp.gamma = sp4.z;
+      uint32_t r = bp.rank[i];
+      r = r < n - 1u ? r : n - 2u;
+      float4* rec = bp.pairs + 4 * (size_t)r;
+      const uint32_t a = emit_slot(bp, rec, LeftSlot(sp, bp.max_leaf), r);
+      const uint32_t b = emit_slot(bp, rec + 2, RightSlot(sp, bp.max_leaf), r);
+      if ((a > b ? a : b) > 0u) atomicMax(&largest, a > b ? a : b);
+    }
+  }
+  __syncthreads();  // (every lane arrives)
+  if (threadIdx.x == 0 && largest != 0u) atomicMax(bp.leafsum + 1, largest);
 }
 
 // hits: 2 uint4 per srt_hit; the first dword is the triangle.

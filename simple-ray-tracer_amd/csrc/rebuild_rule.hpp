@@ -119,5 +119,26 @@ SRT_RULE_HD Slot RightSlot(const Split& sp, uint32_t max_leaf) {
   return c <= (int64_t)max_leaf ? Slot{(uint32_t)(sp.gamma + 1), (uint32_t)c} : Slot{(uint32_t)(sp.gamma + 1), 0u};
 }
 
+// include/srt_rebuild_models.h: record r owns the positions [s, s + c) of the (record, key) order.  Inside a segment the
+// hierarchy is the single-model rule on the segment's own keys and local positions -- a position outside the segment has
+// prefix -1, equal keys tie-break by 32 + clz((i - s) ^ (j - s)) -- so node i (s <= i < s + c - 1) is KarrasSplit over
+// keys + s with local index i - s, moved back to global positions.  Pair and node indices are global: node i is pair i.
+SRT_RULE_HD Split SegmentSplit(const uint32_t* keys, uint32_t s, uint32_t c, uint32_t i) {
+  Split sp = KarrasSplit(keys + s, (int64_t)c, (int64_t)(i - s));
+  sp.first += s;
+  sp.last += s;
+  sp.gamma += s;
+  return sp;
+}
+
+// The root reference of a record with c >= 1 positions from s: a leaf (s, c) when c <= max_leaf (c == 1 always is), else
+// Karras' node s, count 0.
+SRT_RULE_HD Slot SegmentRoot(uint32_t s, uint32_t c, uint32_t max_leaf) {
+  return c <= max_leaf ? Slot{s, c} : Slot{s, 0u};
+}
+
+// The two keys of the (record, key) order in one: records in the high dword.
+SRT_RULE_HD uint64_t RecordKey(uint32_t record, uint32_t morton) { return ((uint64_t)record << 32) | morton; }
+
 }  // namespace rebuild
 }  // namespace srt

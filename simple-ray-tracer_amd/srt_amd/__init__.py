@@ -28,7 +28,7 @@ from . import _lib
 from ._lib import SrtError, check, lib
 
 __all__ = [
-    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "build_lbvh", "UploadModelDataToGPU",
+    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "build_lbvh", "build_lbvh_models", "UploadModelDataToGPU",
     "UpdateModelMatrix", "Camera", "InputState", "progressive_frame", "PointLight", "generate_noise", "glibc_rand", "SrtError",
     "NODE_DTYPE", "BVH_DTYPE", "MAT_DTYPE", "TRI_DTYPE", "VERT_DTYPE", "LIGHT_DTYPE", "RAY_DTYPE",
     "MODEL_LIGHTS", "SPHERE_LIGHTS", "REFERENCE_OBJECTS",
@@ -396,6 +396,35 @@ def build_lbvh(scene: Scene, verts: np.ndarray | None = None, max_leaf: int = 1)
         nodes = nodes[:n_nodes.value].copy()
     bvhs = scene.bvhs.copy()
     bvhs[0]["first_index"], bvhs[0]["count"] = 0, len(nodes)
+    tri_input = None if scene.tri_input is None else scene.tri_input[order]
+    return dataclasses.replace(scene, bvhs=bvhs, nodes=nodes, tris=tris, verts=verts, tri_input=tri_input), order
+
+
+def build_lbvh_models(scene: Scene, verts: np.ndarray | None = None, max_leaf: int = 1) -> tuple["Scene", np.ndarray]:
+    """:func:`build_lbvh` for a scene of any number of models (``srt_bvh_build_lbvh_models``,
+    include/srt_rebuild_models.h): every BVH record gets the linear BVH of its own triangles, a block of ``nodes`` per
+    record in record order; ``tris`` are sorted by (record, key) and ``order`` is position -> index in ``scene.tris``.
+    ``Query(scene, refit=True, rebuild_models=True).rebuild(verts)`` builds the same trees on the device.  A record's
+    ``count`` is its block's node count."""
+    import dataclasses
+
+    verts = scene.verts if verts is None else np.asarray(verts)
+    if verts.dtype != VERT_DTYPE:
+        pos = np.asarray(verts, np.float32).reshape(len(scene.verts), 3)
+        verts = scene.verts.copy()
+        verts["pos"] = pos
+    verts = np.ascontiguousarray(verts).reshape(-1).copy()
+    n = len(scene.tris)
+    nodes, tris, order = np.zeros(max(2 * n - 1, 1), NODE_DTYPE), np.zeros(n, TRI_DTYPE), np.zeros(n, np.uint32)
+    bvhs = np.zeros(len(scene.bvhs), BVH_DTYPE)
+    n_nodes = C.c_uint32(0)
+    check(lib().srt_bvh_build_lbvh_models(_ptr(scene.bvhs), len(scene.bvhs), _ptr(scene.nodes), len(scene.nodes),
+                                          _ptr(scene.tris), n, _ptr(verts), len(verts), int(max_leaf), _ptr(bvhs), _ptr(nodes),
+                                          C.byref(n_nodes), _ptr(tris), _ptr(order)), "srt_bvh_build_lbvh_models")
+    nodes = nodes[:n_nodes.value].copy()
+    starts = [int(b["first_index"]) for b in bvhs] + [len(nodes)]
+    for r in range(len(bvhs)):
+        bvhs[r]["count"] = starts[r + 1] - starts[r]
     tri_input = None if scene.tri_input is None else scene.tri_input[order]
     return dataclasses.replace(scene, bvhs=bvhs, nodes=nodes, tris=tris, verts=verts, tri_input=tri_input), order
 

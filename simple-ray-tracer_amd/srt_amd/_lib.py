@@ -372,6 +372,15 @@ _REBUILD_LEAF_SIGS = {
 }
 REBUILD_LEAF_SYMBOLS = tuple(_REBUILD_LEAF_SIGS)
 
+# include/srt_rebuild_models.h: that rebuild for scenes of several BVH records (its own header and version)
+_REBUILD_MODELS_SIGS = {
+    "srt_rebuild_models_abi_version": (C.c_int, []),
+    "srt_query_enable_rebuild_models": (C.c_int, [P]),
+    "srt_bvh_build_lbvh_models": (C.c_int, [P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, P,
+                                            C.POINTER(C.c_uint32), P, P]),
+}
+REBUILD_MODELS_SYMBOLS = tuple(_REBUILD_MODELS_SIGS)
+
 _lib = None
 
 
@@ -408,7 +417,7 @@ def lib() -> C.CDLL:
                                   + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
                                   + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
                                   + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())
-                                  + list(_REBUILD_LEAF_SIGS.items())):
+                                  + list(_REBUILD_LEAF_SIGS.items()) + list(_REBUILD_MODELS_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -76,17 +76,23 @@ class Query(_Stage):
     ``refit=True`` (``SRT_QUERY_REFIT``, include/srt_refit.h) also uploads the vertex indices and a refit
     schedule, so :meth:`refit` can move the object to new vertex positions on the device.  ``rebuild=True`` (with
     ``refit=True``, one model; include/srt_rebuild.h) also allocates what :meth:`rebuild` needs to give the object a
-    new tree on the device; ``rebuild_leaf=n`` is :meth:`set_rebuild_leaf` at creation.
+    new tree on the device; ``rebuild_leaf=n`` is :meth:`set_rebuild_leaf` at creation.  ``rebuild_models=True`` (with
+    ``refit=True``; include/srt_rebuild_models.h) is ``rebuild=True`` for a scene of any number of models: every BVH
+    record gets a new tree over its own triangles.
     """
 
     _prefix = "srt_query"
 
     def __init__(self, scene: Scene, device: int = 0, stream=None, refit: bool = False, rebuild: bool = False,
-                 rebuild_leaf: int | None = None):
+                 rebuild_leaf: int | None = None, rebuild_models: bool = False):
         super().__init__(device, stream)
         if rebuild and not refit:
             raise ValueError("rebuild=True needs refit=True (include/srt_rebuild.h)")
-        if rebuild_leaf is not None and not rebuild:
+        if rebuild_models and not refit:
+            raise ValueError("rebuild_models=True needs refit=True (include/srt_rebuild_models.h)")
+        if rebuild and rebuild_models:
+            raise ValueError("rebuild=True and rebuild_models=True exclude each other")
+        if rebuild_leaf is not None and not (rebuild or rebuild_models):
             raise ValueError("rebuild_leaf needs rebuild=True (include/srt_rebuild_leaf.h)")
         s = scene
         args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
@@ -96,9 +102,12 @@ class Query(_Stage):
             self._create(*args, SRT_QUERY_REFIT, name="create_ex")
         else:
             self._create(*args)
-        if rebuild:
+        if rebuild or rebuild_models:
             try:
-                self.enable_rebuild()
+                if rebuild_models:
+                    self.enable_rebuild_models()
+                else:
+                    self.enable_rebuild()
                 if rebuild_leaf is not None:
                     self.set_rebuild_leaf(rebuild_leaf)
             except Exception:
@@ -136,6 +145,12 @@ class Query(_Stage):
     def enable_rebuild(self):
         """``srt_query_enable_rebuild``: allocates what :meth:`rebuild` needs (``Query(..., rebuild=True)`` calls it)."""
         check(lib().srt_query_enable_rebuild(self.handle), "srt_query_enable_rebuild")
+
+    def enable_rebuild_models(self):
+        """``srt_query_enable_rebuild_models`` (include/srt_rebuild_models.h): :meth:`enable_rebuild` for a scene of any
+        number of models (``Query(..., rebuild_models=True)`` calls it).  Every triangle must belong to exactly one BVH
+        record."""
+        check(lib().srt_query_enable_rebuild_models(self.handle), "srt_query_enable_rebuild_models")
 
     def set_rebuild_leaf(self, max_leaf: int):
         """``srt_query_set_rebuild_leaf`` (include/srt_rebuild_leaf.h): from the next :meth:`rebuild` on, every subtree

@@ -23,6 +23,12 @@ the pairs, the depth and stack.in_hbm of the tree; and at the amplitudes of --wa
 refit tree, the midpoint tree and the device LBVH of every max_leaf.  max_leaf 1 never calls the setting, so that column
 is the object a caller has without it.
 
+With --models (include/srt_rebuild_models.h) the scene is Rubik beside the knot, two BVH records, and the tool prints one
+JSON line: per max_leaf of --leaf (default 1,4) the time of srt_query_rebuild on the two-record object as above, --repeat
+times over on fresh objects, beside the one-record rebuilds of Rubik and of the knot alone and their sum; the host path
+(readback, a midpoint tree per record built on the host, destroy, create); and the rate of srt_query_closest on the refit
+tree, the host midpoint trees and the device trees of every max_leaf.
+
 Nothing here is asserted: this is a measurement tool.
 """
 from __future__ import annotations
@@ -256,6 +262,98 @@ def run_leaf(args):
         pathlib.Path(args.out).write_text(json.dumps(doc, indent=1) + "\n")
 
 
+def run_models(args):
+    import torch
+
+    import srt_amd as S
+    from bench_queries import surface_rays
+    from bench_refit import closest_rate
+    from srt_amd import _lib
+    from srt_amd import render as R
+    from srt_amd.query import Query
+
+    def dev(a):
+        return torch.from_numpy(a.view(np.float32).reshape(-1, 8).copy()).cuda()
+
+    def timed(scene, vdev, leaf, models):
+        runs, info = [], {}
+        for _ in range(args.repeat):  # a fresh object each time: the spread of the medians is the noise
+            with Query(scene, refit=True, rebuild=not models, rebuild_models=models) as q:
+                if leaf != 1:
+                    q.set_rebuild_leaf(leaf)
+                (med, _, _), _ = time_rebuild(torch, q, vdev, vdev.shape[0], args.batch, args.warmup, args.reps)
+                runs.append(round(med, 5))
+                info = {"pairs": q.get_int("rebuild.pairs"), "depth": q.get_int("rebuild.depth"),
+                        "launches": q.get_int("rebuild.launches"), "records": q.get_int("rebuild.records")}
+        return {"rebuild_ms": round(statistics.median(runs), 5), "rebuild_ms_runs": runs, **info}
+
+    models = [R.rubik_model(ROOT / "tests" / "golden" / "objects"), R.torus_knot_model()]
+    scene = S.Scene.from_models(models)
+    alone = [S.Scene.from_models([m]) for m in models]
+    verts = R.wave_vertices(scene.verts, args.wave)
+    vdev = dev(verts)
+    leaves = args.leaf or [1, 4]
+    r = {"scene": "rubik+knot", "records": len(scene.bvhs), "triangles": len(scene.tris), "vertices": len(verts), "wave": args.wave,
+         "rebuild_batch": args.batch, "warmup": args.warmup, "reps": args.reps, "repeat": args.repeat, "rebuild": [], "rays": args.rays}
+    for leaf in leaves:
+        row = {"max_leaf": leaf, "models": timed(scene, vdev, leaf, True)}
+        for name, one in zip(("rubik", "knot"), alone):
+            row[name + "_alone"] = timed(one, dev(R.wave_vertices(one.verts, args.wave)), leaf, False)
+        row["sum_alone_ms"] = round(row["rubik_alone"]["rebuild_ms"] + row["knot_alone"]["rebuild_ms"], 5)
+        r["rebuild"].append(row)
+
+    # the host path: readback, a midpoint tree per record, destroy, create
+    own = np.zeros(len(scene.tris), np.int64)
+    own[len(alone[0].tris):] = 1
+    lib = _lib.lib()
+
+    def host_scene(pos):
+        return S.Scene.from_models([S.model_from_triangles(pos[scene.tris["v"][own == k]].reshape(-1, 9)) for k in (0, 1)])
+
+    def create(s):
+        h = C.c_void_p()
+        rc = lib.srt_query_create(0, None, S._ptr(s.bvhs), len(s.bvhs), S._ptr(s.nodes), len(s.nodes), S._ptr(s.tris), len(s.tris),
+                                  S._ptr(s.verts), len(s.verts), C.byref(h))
+        assert rc == _lib.SRT_OK, _lib.last_error()
+        return h
+
+    h, ms = create(scene), []
+    for k in range(args.warmup + args.reps):
+        t0 = time.perf_counter()
+        built = host_scene(vdev.cpu().numpy()[:, :3])
+        lib.srt_query_destroy(h)
+        h = create(built)
+        if k >= args.warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    lib.srt_query_destroy(h)
+    r["host_rebuild_ms"] = round(statistics.median(ms), 4)
+    r["host_rebuild_ms_min_max"] = [round(min(ms), 4), round(max(ms), 4)]
+
+    rays = dev(surface_rays(S.refit_scene(scene, verts), args.rays))
+    r["closest"] = {}
+    with Query(scene, refit=True) as qr, Query(host_scene(verts["pos"])) as qm:
+        qr.refit(vdev)
+        for key, qq in (("refit", qr), ("midpoint", qm)):
+            med, lo, hi, _ = closest_rate(torch, qq, rays, args.warmup, args.reps)
+            r["closest"][key] = {"ms": round(med, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "mrays_s": round(args.rays / med / 1e3, 1)}
+    for leaf in leaves:
+        with Query(scene, refit=True, rebuild_models=True, rebuild_leaf=leaf) as ql:
+            ql.rebuild(vdev)
+            med, lo, hi, _ = closest_rate(torch, ql, rays, args.warmup, args.reps)
+            r["closest"][f"models_leaf_{leaf}"] = {"ms": round(med, 4), "ms_min_max": [round(lo, 4), round(hi, 4)],
+                                                   "mrays_s": round(args.rays / med / 1e3, 1)}
+    print(json.dumps(r), flush=True)
+    if args.out:
+        doc = {"tool": "tools/bench_rebuild.py --models", "device": torch.cuda.get_device_name(0),
+               "code_hash": lib.srt_code_hash().decode(),
+               "timing": "rebuild: torch.cuda.Event pair around a batch of srt_query_rebuild calls on the object's stream, per call "
+                         "(each call synchronises once); the median of --reps such batches, --repeat times over on fresh objects; "
+                         "host rebuild: host wall clock of readback + a host midpoint build per record + srt_query_destroy + "
+                         "srt_query_create; closest: event pair around one enqueued srt_query_closest",
+               "result": r}
+        pathlib.Path(args.out).write_text(json.dumps(doc, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--wave", type=float, default=WAVE_AMPLITUDE)
@@ -267,6 +365,8 @@ def main():
     ap.add_argument("--out", help="write the results to this JSON file")
     ap.add_argument("--leaf", type=lambda t: [int(x) for x in t.split(",")], metavar="L,L,...",
                     help="measure the leaf collapse at these max_leaf values (srt_rebuild_leaf.h) instead")
+    ap.add_argument("--models", action="store_true",
+                    help="measure the two-record scene Rubik + knot (srt_rebuild_models.h) instead; --leaf defaults to 1,4")
     ap.add_argument("--waves", type=lambda t: [float(x) for x in t.split(",")], default=[0.25, 1.0, 4.0], metavar="A,A,...",
                     help="with --leaf: the amplitudes the query rate is measured at")
     ap.add_argument("--repeat", type=int, default=3, help="with --leaf: rebuild timings per max_leaf, each on a fresh object")
@@ -277,7 +377,7 @@ def main():
         ap.error("at least 3 warm-up rounds and 10 measured ones")
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
 
-    (run_leaf if args.leaf else run)(args)
+    (run_models if args.models else run_leaf if args.leaf else run)(args)
 
 
 if __name__ == "__main__":
