@@ -4,7 +4,8 @@ against the CPU oracle on the host-built arrays, the oracle's hit position mappe
 
 tests/test_rebuild_leaf_api.py holds the mirror to a numpy restatement of the rule.  Scenes of tests/rebuild_ref.py: Rubik;
 the lifted 24 x 24 quad grid; 64 copies of one triangle (every key equal); three triangles (max_leaf 2: a leaf of one and
-a leaf of two; max_leaf 4: a leaf root); one triangle (a leaf root); a mesh with two vertex indices out of range.
+a leaf of two; max_leaf 4: a leaf root); one triangle (a leaf root); a mesh with two vertex indices out of range.  And
+511 copies of one triangle at max_leaf 255 (tests/scale_scenes.py): a leaf of 255, the largest count there is.
 """
 import numpy as np
 import pytest
@@ -12,6 +13,7 @@ import pytest
 import rebuild_leaf_ref as LR
 import rebuild_ref as BR
 import refit_ref as RR
+import scale_scenes as SC
 import srt_amd as S
 from conftest import OBJECTS, bits_equal
 from oracle import pyoracle as O
@@ -58,6 +60,22 @@ def cases(rubik):
     return Cases(rubik)
 
 
+def pairs_loop(nodes):
+    """The uint32 [4 m, 4] pair rows a mirror-built node array stands for, pair by pair: pair r holds nodes 2r + 1 and
+    2r + 2 (tests/scale_scenes.py pairs_from_nodes is the same without the loop, held equal on the CPU)."""
+    m = (len(nodes) - 1) // 2
+    want = np.zeros((4 * m, 4), np.uint32)  # the .w dwords by pair number
+    for r in range(m):
+        for slot in (0, 1):
+            node = nodes[2 * r + 1 + slot]
+            count = int(node["count"])
+            want[4 * r + 2 * slot, 3] = int(node["first"]) if count else (int(node["first"]) - 1) // 2
+            want[4 * r + 2 * slot + 1, 3] = count
+            want[4 * r + 2 * slot, :3] = node["min"].view(np.uint32)
+            want[4 * r + 2 * slot + 1, :3] = node["max"].view(np.uint32)
+    return want
+
+
 def check_structure(q, built, order):
     """The device layout against the mirror's node array: the walk from the root (leaf or not, first triangle, count,
     the six box dwords), the pair numbering (pair r holds nodes 2r + 1 and 2r + 2), the pair rows the object reports,
@@ -67,15 +85,7 @@ def check_structure(q, built, order):
     assert (roots[2:4] == roots[0:2]).all()  # the ghost root is the root
     m = (len(built.nodes) - 1) // 2
     assert pairs.shape == (4 * max(m, 1), 4)
-    want = np.zeros((4 * m, 4), np.uint32)  # the .w dwords by pair number
-    for r in range(m):
-        for slot in (0, 1):
-            node = built.nodes[2 * r + 1 + slot]
-            count = int(node["count"])
-            want[4 * r + 2 * slot, 3] = int(node["first"]) if count else (int(node["first"]) - 1) // 2
-            want[4 * r + 2 * slot + 1, 3] = count
-            want[4 * r + 2 * slot, :3] = node["min"].view(np.uint32)
-            want[4 * r + 2 * slot + 1, :3] = node["max"].view(np.uint32)
+    want = pairs_loop(built.nodes)
     assert (pairs[:4 * m] == want).all(), f"{(pairs[:4 * m] != want).sum()} pair dwords differ"
     assert (tris == BR.layout_tris(built)).all(), f"{(tris != BR.layout_tris(built)).sum()} tris dwords differ"
     assert (q.tri_order() == order).all()
@@ -129,6 +139,44 @@ def test_structure_hits_and_counters_after_a_collapsed_rebuild(torch, cases, nam
         assert counts == ([0, 1, 2] if max_leaf == 2 else [3])  # a 1-leaf and a 2-leaf; a leaf root
     if name == "one":
         assert len(built.nodes) == 1
+    hit = check_hits(built, order, hits, oracle)
+    assert (occ == hit).all()
+    assert hit.sum() >= 100, "the rays must find the mesh"
+
+
+def test_a_leaf_of_255_keeps_packed_stack_entries(torch):
+    """The largest max_leaf there is: 511 copies of one triangle (every key equal, so the positions decide: the root
+    splits [0, 255] from [256, 510], and the right side is one leaf of 255 -- tests/test_scale_scenes.py holds the mirror
+    to that).  A count of 255 still fits the packed stack entry (csrc/query_host.cpp: max_leaf < 256)."""
+    from srt_amd import SrtError, _lib
+    from srt_amd.query import Query
+
+    scene, verts = SC.leaf255_scene()
+    built, order = S.build_lbvh(scene, verts, max_leaf=255)
+    assert len(scene.tris) == 511 and sorted(int(c) for c in built.nodes["count"]) == [0, 0, 128, 128, 255]
+    rays = scene_rays("copies", built)  # from outside the box and aimed at the copies
+    oracle = O.Oracle(built).trace_closest(1, rays)
+    stream = torch.cuda.Stream()
+    with Query(scene, stream=stream, refit=True, rebuild=True) as q:
+        with pytest.raises(SrtError) as e:
+            q.set_rebuild_leaf(256)
+        assert e.value.code == _lib.SRT_ERR_INVALID and "[1, 255]" in str(e.value)
+        del e
+        assert q.get_int("rebuild.leaf") == 1
+        q.set_rebuild_leaf(255)
+        assert q.get_int("rebuild.leaf") == 255
+        with torch.cuda.stream(stream):
+            v = verts_dev(torch, verts)
+            dev = to_dev(torch, rays)
+            q.rebuild(v)
+            hits = q.closest(dev)
+            occ = q.occluded(dev)
+        stream.synchronize()
+        hits, occ = hits.numpy(), occ.cpu().numpy()
+        assert q.get_int("rebuild.max_leaf") == 255 and q.get_int("stack.packed") == 1
+        check_structure(q, built, order)
+        check_counters(q, scene, built, 255)
+        assert q.get_int("rebuild.count") == 1
     hit = check_hits(built, order, hits, oracle)
     assert (occ == hit).all()
     assert hit.sum() >= 100, "the rays must find the mesh"
