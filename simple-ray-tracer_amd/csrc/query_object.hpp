@@ -20,6 +20,15 @@ namespace rebuild {
 // d_pairs / d_triples / d_schedule are the LBVH's arrays-to-be; that rebuild exchanges them with the object's,
 // and they then hold the creation-order index triples (kept: every rebuild sorts from them) and the replaced
 // tree's pairs and schedule (freed after that rebuild's synchronisation).
+//
+// Which arrays exist (the others stay null):
+//   always                    d_pairs, d_triples, d_schedule, d_vals_in, d_keys, d_order, d_temp, d_parent, d_height,
+//                             d_zeroed
+//   one record                d_keys_in (the 32-bit sort's input; d_keys is its output), d_box
+//   two records or more       d_keys64_in, d_keys64 (the 64-bit sort; d_keys holds the sorted low dwords), d_owner,
+//                             d_pos_rec, d_seg; the records' boxes follow the arrival words in d_zeroed
+//   from the first max_leaf   d_split, d_flags, d_rank, d_leafsum, d_scan_temp (counted in leaf_bytes, not in bytes)
+//   above 1, and n > 1
 struct State {
   stage::DevPtr<float4> d_pairs;
   stage::DevPtr<uint4> d_triples;
@@ -28,7 +37,7 @@ struct State {
   stage::DevPtr<uint8_t> d_temp;                                  // its temporary storage
   size_t temp_bytes = 0;
   stage::DevPtr<uint32_t> d_parent, d_height;
-  stage::DevPtr<uint32_t> d_zeroed;  // zeroed by every rebuild: counts, cursor, then the arrival words
+  stage::DevPtr<uint32_t> d_zeroed;  // zeroed by every rebuild: counts, cursor, the arrival words, the records' boxes
   stage::DevPtr<float> d_box;        // the scene box, then the partial boxes
   size_t bytes = 0;
   int count = 0, launches = 0, depth = 0;
@@ -43,11 +52,10 @@ struct State {
   size_t scan_temp_bytes = 0, leaf_bytes = 0;
   uint32_t leaf_summary[2] = {};     // what the last collapsed rebuild read back from d_leafsum
   uint32_t pairs = 0, largest_leaf = 0;  // of the last rebuild's tree
-  // srt_query_enable_rebuild_models (include/srt_rebuild_models.h); the arrays only with two records or more, where
-  // d_keys_in stays null (the sort's input is d_keys64_in) and d_box too (the boxes follow the arrival words in d_zeroed)
-  bool models = false;
+  // include/srt_rebuild_models.h
+  bool models = false;                       // enabled by srt_query_enable_rebuild_models
   uint32_t records = 1;
-  Segments segments;                         // s_r, n_r: fixed when enabled
+  Segments segments;                         // s_r, n_r: fixed when enabled (one record: 0, n)
   stage::DevPtr<uint32_t> d_owner, d_pos_rec;  // n each: creation index -> record, position -> record
   stage::DevPtr<uint2> d_seg;                  // per record
   stage::DevPtr<uint64_t> d_keys64_in, d_keys64;

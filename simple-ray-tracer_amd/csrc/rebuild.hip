@@ -1,9 +1,10 @@
-// rebuild.hip -- the device rebuild of include/srt_rebuild.h: the rebuild data of a query object, the launches of
-// rebuild.hpp's kernels around hipcub's radix sort, the one readback, the new schedule and stack plan, the
-// refit that fills the boxes, and the hit remap; and include/srt_rebuild_leaf.h's max_leaf, which puts a range kernel,
-// hipcub's scan and an emit kernel in the hierarchy kernel's place; and include/srt_rebuild_models.h's rebuild of several
-// BVH records at once (EnableModels, RebuildModels: segment bounds, a 64-bit sort).  A translation unit of its own beside
-// query.hip and refit.hip.
+// rebuild.hip -- the device rebuild of include/srt_rebuild.h, srt_rebuild_leaf.h and srt_rebuild_models.h: the rebuild
+// data of a query object (Enable, SetLeaf), and one Rebuild -- the launches of rebuild.hpp's kernels around hipcub's
+// radix sort, the one readback, the new schedule and stack plan, the refit that fills the boxes -- and the hit remap.
+// The case enters Rebuild as data: the records (one: the scene box and a 32-bit sort; several: a box per record and a
+// 64-bit (record, key) sort, and the SEG instances of the kernels), max_leaf (above 1 a range kernel, hipcub's scan and
+// an emit kernel stand in the hierarchy kernel's place), and what SegmentShape says of the segments.  A translation
+// unit of its own beside query.hip and refit.hip.
 #include <hip/hip_runtime.h>
 #include <hipcub/device/device_radix_sort.hpp>
 #include <hipcub/device/device_scan.hpp>
@@ -30,9 +31,33 @@ constexpr int kKeyBits = 30;
 
 uint32_t Blocks(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
+int RecordBits(uint32_t records) {
+  int bits = 1;
+  while (bits < 32 && (1ull << bits) < records) ++bits;
+  return bits;
+}
+
+// One record: the 30 key bits.  Several: the (record, key) sort over bits [0, 32 + the records' bits) of the 64-bit
+// keys.  Stable, as every radix sort is.
 hipError_t Sort(State& st, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
+  if (st.records > 1)
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint64_t*)st.d_keys64_in.get(), st.d_keys64.get(),
+                                              (const uint32_t*)st.d_vals_in.get(), st.d_order.get(), n, 0,
+                                              32 + RecordBits(st.records), stream);
   return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint32_t*)st.d_keys_in.get(), st.d_keys.get(),
                                             (const uint32_t*)st.d_vals_in.get(), st.d_order.get(), n, 0, kKeyBits, stream);
+}
+
+// d_zeroed: counts, cursor, the arrival words, and with several records their boxes.
+size_t ZeroedWords(uint32_t n, uint32_t records) {
+  return 2 * (size_t)kHeightBins + (n - 1) + (records > 1 ? 8 * (size_t)records : 0);
+}
+
+// An allocation the object reports: `total` is rebuild.bytes or rebuild.leaf_bytes.
+template <class T>
+hipError_t Alloc(stage::DevPtr<T>& p, size_t bytes, size_t& total) {
+  total += bytes;
+  return p.Alloc(bytes);
 }
 
 // rank = the exclusive sum of the n survival flags (the last is 0, so rank[n - 1] is the number of survivors)
@@ -89,35 +114,75 @@ int Adopt(srt_query* q, const srt_vertex* verts_dev, int launches, uint32_t m, u
 
 }  // namespace
 
+// The rebuild data of an object of q->n_bvhs records.  With two or more, first the owners from the object's own pairs and
+// roots, and beside the common arrays 64-bit sort keys, the per-record boxes behind the arrival words, and the segment
+// arrays; with one, the segment is [0, n) and the arrays are the scene box's and the 32-bit keys'.
 int Enable(srt_query* q) {
   STAGE_HIP_OK(hipSetDevice(q->device));
+  const uint32_t n = q->n_tris, n_pairs = n - 1, records = q->n_bvhs;
+  const bool seg = records > 1;
+  std::vector<uint32_t> owner(n, 0u);
+  std::string err;
+  if (seg) {
+    STAGE_HIP_OK(hipStreamSynchronize(q->stream));
+    std::vector<query::F4> pairs(q->pairs_bytes / sizeof(query::F4)), roots(q->roots_bytes / sizeof(query::F4));
+    STAGE_HIP_OK(hipMemcpy(pairs.data(), q->d_pairs, q->pairs_bytes, hipMemcpyDeviceToHost));
+    STAGE_HIP_OK(hipMemcpy(roots.data(), q->d_roots, q->roots_bytes, hipMemcpyDeviceToHost));
+    if (roots.size() < 2 * ((size_t)records + 1) || pairs.size() < 4 * (size_t)q->n_pairs) return SRT_ERR_STATE;
+    if (int rc = OwnersFromLayout(pairs.data(), q->n_pairs, roots.data(), records, n, owner.data(), &err)) {
+      srt::SetError(err);
+      return rc;
+    }
+  }
   std::unique_ptr<State> st(new State());
-  const uint32_t n = q->n_tris, n_pairs = n - 1;
-  const size_t pairs = 4 * sizeof(float4) * (size_t)(n_pairs ? n_pairs : 1u);
-  const size_t sched = sizeof(uint32_t) * ((size_t)n_pairs + kHeightBins + 1);
-  const size_t per_tri = sizeof(uint32_t) * (size_t)n;
-  const size_t zeroed = sizeof(uint32_t) * (2 * (size_t)kHeightBins + n_pairs);
-  const size_t box = sizeof(float) * 8 * (1 + (size_t)kBoxBlocks);
-  STAGE_HIP_OK(st->d_pairs.Alloc(pairs));
-  STAGE_HIP_OK(st->d_triples.Alloc(sizeof(uint4) * (size_t)n));
-  STAGE_HIP_OK(st->d_schedule.Alloc(sched));
-  STAGE_HIP_OK(st->d_keys_in.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_vals_in.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_keys.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_order.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_parent.Alloc(sizeof(uint32_t) * (2 * (size_t)n)));
-  STAGE_HIP_OK(st->d_height.Alloc(sizeof(uint32_t) * (size_t)(n_pairs ? n_pairs : 1u)));
-  STAGE_HIP_OK(st->d_zeroed.Alloc(zeroed));
-  STAGE_HIP_OK(st->d_box.Alloc(box));
+  st->records = records;
+  st->segments = SegmentsOf(owner.data(), n, records);
+  if (int rc = CheckSegments(st->segments, &err)) {
+    srt::SetError(err);
+    return rc;
+  }
+  const size_t per_tri = sizeof(uint32_t) * (size_t)n, per_pair = sizeof(uint32_t) * (size_t)(n_pairs ? n_pairs : 1u);
+  const size_t seg_bytes = sizeof(uint2) * (size_t)records;
+  size_t& bytes = st->bytes;
+  STAGE_HIP_OK(Alloc(st->d_pairs, 4 * sizeof(float4) * (size_t)(n_pairs ? n_pairs : 1u), bytes));
+  STAGE_HIP_OK(Alloc(st->d_triples, sizeof(uint4) * (size_t)n, bytes));
+  STAGE_HIP_OK(Alloc(st->d_schedule, sizeof(uint32_t) * ((size_t)n_pairs + kHeightBins + 1), bytes));
+  STAGE_HIP_OK(Alloc(st->d_vals_in, per_tri, bytes));
+  STAGE_HIP_OK(Alloc(st->d_keys, per_tri, bytes));
+  STAGE_HIP_OK(Alloc(st->d_order, per_tri, bytes));
+  STAGE_HIP_OK(Alloc(st->d_parent, 2 * per_tri, bytes));
+  STAGE_HIP_OK(Alloc(st->d_height, per_pair, bytes));
+  STAGE_HIP_OK(Alloc(st->d_zeroed, sizeof(uint32_t) * ZeroedWords(n, records), bytes));
+  if (seg) {
+    STAGE_HIP_OK(Alloc(st->d_keys64_in, 2 * per_tri, bytes));
+    STAGE_HIP_OK(Alloc(st->d_keys64, 2 * per_tri, bytes));
+    STAGE_HIP_OK(Alloc(st->d_owner, per_tri, bytes));
+    STAGE_HIP_OK(Alloc(st->d_pos_rec, per_tri, bytes));
+    STAGE_HIP_OK(Alloc(st->d_seg, seg_bytes, bytes));
+  } else {
+    STAGE_HIP_OK(Alloc(st->d_keys_in, per_tri, bytes));
+    STAGE_HIP_OK(Alloc(st->d_box, sizeof(float) * 8 * (1 + (size_t)kBoxBlocks), bytes));
+  }
   size_t temp = 0;
   STAGE_HIP_OK(Sort(*st, n, q->stream, nullptr, temp));  // the size only
   st->temp_bytes = temp ? temp : 16;
-  STAGE_HIP_OK(st->d_temp.Alloc(st->temp_bytes));
+  STAGE_HIP_OK(Alloc(st->d_temp, st->temp_bytes, bytes));
+  std::vector<uint32_t> pos_rec;
+  std::vector<uint2> segs;
+  if (seg) {
+    pos_rec.resize(n);
+    segs.resize(records);
+    for (uint32_t r = 0; r < records; ++r) {
+      segs[r] = make_uint2(st->segments.first[r], st->segments.count[r]);
+      for (uint32_t k = 0; k < st->segments.count[r]; ++k) pos_rec[st->segments.first[r] + k] = r;
+    }
+    STAGE_HIP_OK(hipMemcpyAsync(st->d_owner, owner.data(), per_tri, hipMemcpyHostToDevice, q->stream));
+    STAGE_HIP_OK(hipMemcpyAsync(st->d_pos_rec, pos_rec.data(), per_tri, hipMemcpyHostToDevice, q->stream));
+    STAGE_HIP_OK(hipMemcpyAsync(st->d_seg, segs.data(), seg_bytes, hipMemcpyHostToDevice, q->stream));
+  }
   // one triangle: the order is the identity for good (its rebuild is a refit)
   STAGE_HIP_OK(hipMemsetAsync(st->d_order, 0, per_tri, q->stream));
-  STAGE_HIP_OK(hipStreamSynchronize(q->stream));
-  st->bytes = pairs + sizeof(uint4) * (size_t)n + sched + 4 * per_tri + sizeof(uint32_t) * (2 * (size_t)n) +
-              sizeof(uint32_t) * (size_t)(n_pairs ? n_pairs : 1u) + zeroed + box + st->temp_bytes;
+  STAGE_HIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
   q->rebuild = std::move(st);
   return SRT_OK;
 }
@@ -131,15 +196,16 @@ int SetLeaf(srt_query* q, uint32_t max_leaf) {
     stage::DevPtr<uint4> split;
     stage::DevPtr<uint32_t> flags, rank, leafsum;
     stage::DevPtr<uint8_t> scan_temp;
-    const size_t per_tri = sizeof(uint32_t) * (size_t)n, sb = sizeof(uint4) * (size_t)(n - 1);
-    STAGE_HIP_OK(split.Alloc(sb));
-    STAGE_HIP_OK(flags.Alloc(per_tri));
-    STAGE_HIP_OK(rank.Alloc(per_tri));
-    STAGE_HIP_OK(leafsum.Alloc(2 * sizeof(uint32_t)));
+    const size_t per_tri = sizeof(uint32_t) * (size_t)n;
+    size_t bytes = 0;
+    STAGE_HIP_OK(Alloc(split, sizeof(uint4) * (size_t)(n - 1), bytes));
+    STAGE_HIP_OK(Alloc(flags, per_tri, bytes));
+    STAGE_HIP_OK(Alloc(rank, per_tri, bytes));
+    STAGE_HIP_OK(Alloc(leafsum, 2 * sizeof(uint32_t), bytes));
     size_t temp = 0;
     STAGE_HIP_OK(Scan(flags, rank, n, q->stream, nullptr, temp));  // the size only: nothing is enqueued
     temp = temp ? temp : 16;
-    STAGE_HIP_OK(scan_temp.Alloc(temp));
+    STAGE_HIP_OK(Alloc(scan_temp, temp, bytes));
     // (every allocation succeeded: only now does the state change)
     st.scan_temp_bytes = temp;
     st.d_flags = std::move(flags);
@@ -147,11 +213,61 @@ int SetLeaf(srt_query* q, uint32_t max_leaf) {
     st.d_split = std::move(split);
     st.d_leafsum = std::move(leafsum);
     st.d_scan_temp = std::move(scan_temp);
-    st.leaf_bytes = sb + 2 * per_tri + 2 * sizeof(uint32_t) + st.scan_temp_bytes;
+    st.leaf_bytes = bytes;
   }
   st.max_leaf = max_leaf;
   return SRT_OK;
 }
+
+namespace {
+
+// The kernels' view of the state and the object: every array the case has (the others stay null).
+BParams Bind(const State& st, const srt_query* q, const srt_vertex* verts_dev) {
+  const uint32_t n = q->n_tris;
+  BParams bp;
+  std::memset(&bp, 0, sizeof bp);
+  bp.pairs = q->d_pairs;
+  bp.roots = q->d_roots;
+  bp.triples0 = st.d_triples;
+  bp.triples = q->d_triples;
+  bp.verts = reinterpret_cast<const float4*>(verts_dev);
+  bp.vals_in = st.d_vals_in;
+  bp.keys = st.d_keys;
+  bp.order = st.d_order;
+  bp.parent = st.d_parent;
+  bp.counts = st.d_zeroed;
+  bp.cursor = st.d_zeroed + kHeightBins;
+  bp.arrive = st.d_zeroed + 2 * kHeightBins;
+  bp.height = st.d_height;
+  bp.schedule = q->d_schedule;
+  bp.n_verts = q->n_verts;
+  bp.n_tris = n;
+  bp.n_records = st.records;
+  if (st.records > 1) {
+    bp.owner = st.d_owner;
+    bp.pos_rec = st.d_pos_rec;
+    bp.seg = st.d_seg;
+    bp.seg_box = bp.arrive + (n - 1);
+    bp.keys64_in = st.d_keys64_in;
+    bp.keys64 = st.d_keys64;
+    bp.keys_out = st.d_keys;
+  } else {
+    bp.box = st.d_box;
+    bp.box_partial = st.d_box + 8;
+    bp.keys_in = st.d_keys_in;
+    bp.box_blocks = Blocks(n) < kBoxBlocks ? Blocks(n) : kBoxBlocks;
+  }
+  if (st.max_leaf > 1) {
+    bp.split = st.d_split;
+    bp.flags = st.d_flags;
+    bp.rank = st.d_rank;
+    bp.leafsum = st.d_leafsum;
+    bp.max_leaf = st.max_leaf;
+  }
+  return bp;
+}
+
+}  // namespace
 
 int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
   STAGE_HIP_OK(hipSetDevice(q->device));
@@ -166,10 +282,16 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
     ++st.count;
     return SRT_OK;
   }
-  const uint32_t n_pairs = n - 1;       // of Karras' hierarchy, and the pair array's capacity
+  const uint32_t n_pairs = n - 1;      // the pair array's capacity
   const uint32_t max_leaf = st.max_leaf;
-  const bool collapse = max_leaf > 1;   // rules 4a-4c; false: exactly srt_rebuild.h's launches
-  const bool leaf_root = n <= max_leaf; // m == 0: the sort, the root, the refit
+  const bool seg = st.records > 1;
+  const bool collapse = max_leaf > 1;  // rules 4a-4c; false: exactly srt_rebuild.h's launches
+  uint32_t karras_pairs = 0, root_leaf = 0;  // what the segments say before the device ran
+  SegmentShape(st.segments, max_leaf, &karras_pairs, &root_leaf);
+  // one record of n <= max_leaf triangles: the sort, the root, the refit.  (Several records that are all leaf roots go
+  // through the collapse's kernels, which write every root; their m is 0 too.)
+  const bool root_only = !seg && karras_pairs == 0;
+  const bool emitted = collapse && !root_only;  // leafsum is this rebuild's
   const bool first_time = st.count == 0;
   if (first_time) {
     // the LBVH's arrays take the object's place; the state keeps the creation-order triples for every later
@@ -178,261 +300,58 @@ int Rebuild(srt_query* q, const srt_vertex* verts_dev) {
     std::swap(st.d_triples, q->d_triples);
     std::swap(st.d_schedule, q->d_schedule);
   }
-  BParams bp;
-  std::memset(&bp, 0, sizeof bp);
-  bp.pairs = q->d_pairs;
-  bp.roots = q->d_roots;
-  bp.triples0 = st.d_triples;
-  bp.triples = q->d_triples;
-  bp.verts = reinterpret_cast<const float4*>(verts_dev);
-  bp.box = st.d_box;
-  bp.box_partial = st.d_box + 8;
-  bp.keys_in = st.d_keys_in;
-  bp.vals_in = st.d_vals_in;
-  bp.keys = st.d_keys;
-  bp.order = st.d_order;
-  bp.parent = st.d_parent;
-  bp.counts = st.d_zeroed;
-  bp.cursor = st.d_zeroed + kHeightBins;
-  bp.arrive = st.d_zeroed + 2 * kHeightBins;
-  bp.height = st.d_height;
-  bp.schedule = q->d_schedule;
-  bp.n_verts = q->n_verts;
-  bp.n_tris = n;
-  bp.box_blocks = Blocks(n) < kBoxBlocks ? Blocks(n) : kBoxBlocks;
-  if (collapse) {
-    bp.split = st.d_split;
-    bp.flags = st.d_flags;
-    bp.rank = st.d_rank;
-    bp.leafsum = st.d_leafsum;
-    bp.max_leaf = max_leaf;
-  }
+  const BParams bp = Bind(st, q, verts_dev);
   hipStream_t s = q->stream;
   int launches = 0;
-#define REBUILD_LAUNCH(kernel, blocks)                                            \
-  do {                                                                            \
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, bp);             \
-    STAGE_HIP_OK(hipGetLastError());                                              \
-    ++launches;                                                                   \
-  } while (0)
-  STAGE_HIP_OK(hipMemsetAsync(st.d_zeroed, 0, sizeof(uint32_t) * (2 * (size_t)kHeightBins + n_pairs), s));
-  REBUILD_LAUNCH(box_partial_kernel, bp.box_blocks);
-  REBUILD_LAUNCH(box_final_kernel, 1);
-  REBUILD_LAUNCH(keys_kernel, Blocks(n));
+  auto launch = [&](void (*kernel)(BParams), uint32_t blocks) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, bp);
+    ++launches;
+    return hipGetLastError();
+  };
+  STAGE_HIP_OK(hipMemsetAsync(st.d_zeroed, 0, sizeof(uint32_t) * ZeroedWords(n, st.records), s));
+  if (seg) {
+    STAGE_HIP_OK(launch(seg_box_kernel, Blocks(n)));
+  } else {
+    STAGE_HIP_OK(launch(box_partial_kernel, bp.box_blocks));
+    STAGE_HIP_OK(launch(box_final_kernel, 1));
+  }
+  STAGE_HIP_OK(launch(seg ? keys_kernel<true> : keys_kernel<false>, Blocks(n)));
   size_t temp = st.temp_bytes;
   STAGE_HIP_OK(Sort(st, n, s, st.d_temp, temp));
   ++launches;  // (the sort's own launches are hipcub's business: counted as one)
-  if (leaf_root) {
-    // no pair: the positions' order and the root are the tree (pair 0, which srt_query_copy_layout still copies,
-    // keeps nothing of the tree before)
-    REBUILD_LAUNCH(permute_kernel, Blocks(n));
-    REBUILD_LAUNCH(root_leaf_kernel, 1);
-    STAGE_HIP_OK(hipMemsetAsync(q->d_pairs, 0, 4 * sizeof(float4), s));
-  } else if (collapse) {
-    REBUILD_LAUNCH(range_kernel, Blocks(n));
-    size_t scan_temp = st.scan_temp_bytes;
-    STAGE_HIP_OK(Scan(st.d_flags, st.d_rank, n, s, st.d_scan_temp, scan_temp));
-    ++launches;  // (hipcub's business again: counted as one)
-    REBUILD_LAUNCH(emit_kernel, Blocks(n_pairs));
-    REBUILD_LAUNCH(permute_kernel, Blocks(n));
-    REBUILD_LAUNCH(climb_kernel<true>, Blocks(n));
-    REBUILD_LAUNCH(schedule_kernel<true>, Blocks(n_pairs));
+  STAGE_HIP_OK(launch(seg ? permute_kernel<true> : permute_kernel<false>, Blocks(n)));
+  if (root_only) {
+    STAGE_HIP_OK(launch(root_leaf_kernel, 1));
   } else {
-    REBUILD_LAUNCH(karras_kernel, Blocks(n_pairs));
-    REBUILD_LAUNCH(permute_kernel, Blocks(n));
-    REBUILD_LAUNCH(climb_kernel<false>, Blocks(n));
-    REBUILD_LAUNCH(schedule_kernel<false>, Blocks(n_pairs));
+    if (collapse) {
+      STAGE_HIP_OK(launch(seg ? range_kernel<true> : range_kernel<false>, Blocks(n)));
+      size_t scan_temp = st.scan_temp_bytes;
+      STAGE_HIP_OK(Scan(st.d_flags, st.d_rank, n, s, st.d_scan_temp, scan_temp));
+      ++launches;  // (hipcub's business again: counted as one)
+      STAGE_HIP_OK(launch(seg ? emit_kernel<true> : emit_kernel<false>, Blocks(n)));
+    } else {
+      STAGE_HIP_OK(launch(seg ? karras_kernel<true> : karras_kernel<false>, Blocks(n)));
+    }
+    STAGE_HIP_OK(launch(collapse ? climb_kernel<true> : climb_kernel<false>, Blocks(n)));
+    STAGE_HIP_OK(launch(collapse ? (seg ? schedule_kernel<true, true> : schedule_kernel<true, false>)
+                                 : (seg ? schedule_kernel<false, true> : schedule_kernel<false, false>),
+                        Blocks(n_pairs)));
   }
-#undef REBUILD_LAUNCH
+  if (karras_pairs == 0 && collapse)  // no pair at all: pair 0, which srt_query_copy_layout still copies, keeps nothing
+    STAGE_HIP_OK(hipMemsetAsync(q->d_pairs, 0, 4 * sizeof(float4), s));
   // the one synchronisation: the pair counts per height, and of a collapsed tree its pairs and its largest leaf
   STAGE_HIP_OK(hipMemcpyAsync(st.summary, st.d_zeroed, sizeof(uint32_t) * kHeightBins, hipMemcpyDeviceToHost, s));
-  if (collapse && !leaf_root)
-    STAGE_HIP_OK(hipMemcpyAsync(st.leaf_summary, st.d_leafsum, sizeof st.leaf_summary, hipMemcpyDeviceToHost, s));
+  if (emitted) STAGE_HIP_OK(hipMemcpyAsync(st.leaf_summary, st.d_leafsum, sizeof st.leaf_summary, hipMemcpyDeviceToHost, s));
   STAGE_HIP_OK(hipStreamSynchronize(s));
   if (first_time) {  // nothing enqueued reads the replaced tree any more
     st.d_pairs.Free();
     st.d_schedule.Free();
   }
-  const uint32_t m = leaf_root ? 0u : (collapse ? st.leaf_summary[0] : n_pairs);
-  const uint32_t largest = leaf_root ? n : (collapse ? st.leaf_summary[1] : 1u);
-  return Adopt(q, verts_dev, launches, m, m, largest, !collapse || leaf_root || LeafSummaryValid(m, largest, n, max_leaf));
-}
-
-// -- include/srt_rebuild_models.h -----------------------------------------------------------------------------------------
-namespace {
-
-// The (record, key) sort: bits [0, 32 + the records' bits) of the 64-bit keys; stable, as every radix sort is.
-int RecordBits(uint32_t records) {
-  int bits = 1;
-  while (bits < 32 && (1ull << bits) < records) ++bits;
-  return bits;
-}
-
-hipError_t SortModels(State& st, uint32_t n, hipStream_t stream, void* temp, size_t& temp_bytes) {
-  return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, (const uint64_t*)st.d_keys64_in.get(), st.d_keys64.get(),
-                                            (const uint32_t*)st.d_vals_in.get(), st.d_order.get(), n, 0,
-                                            32 + RecordBits(st.records), stream);
-}
-
-size_t ZeroedWords(uint32_t n, uint32_t records) { return 2 * (size_t)kHeightBins + (n - 1) + 8 * (size_t)records; }
-
-}  // namespace
-
-// Two records or more (one record is Enable above, unchanged): the owners from the object's own pairs and roots, then
-// Enable's allocations with 64-bit sort keys, the per-record boxes behind the arrival words, and the segment arrays.
-int EnableModels(srt_query* q) {
-  STAGE_HIP_OK(hipSetDevice(q->device));
-  const uint32_t n = q->n_tris, n_pairs = n - 1, records = q->n_bvhs;
-  STAGE_HIP_OK(hipStreamSynchronize(q->stream));
-  std::vector<query::F4> pairs(q->pairs_bytes / sizeof(query::F4)), roots(q->roots_bytes / sizeof(query::F4));
-  STAGE_HIP_OK(hipMemcpy(pairs.data(), q->d_pairs, q->pairs_bytes, hipMemcpyDeviceToHost));
-  STAGE_HIP_OK(hipMemcpy(roots.data(), q->d_roots, q->roots_bytes, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> owner(n);
-  std::string err;
-  if (roots.size() < 2 * ((size_t)records + 1) || pairs.size() < 4 * (size_t)q->n_pairs) return SRT_ERR_STATE;
-  if (int rc = OwnersFromLayout(pairs.data(), q->n_pairs, roots.data(), records, n, owner.data(), &err)) {
-    srt::SetError(err);
-    return rc;
-  }
-  std::unique_ptr<State> st(new State());
-  st->models = true;
-  st->records = records;
-  st->segments = SegmentsOf(owner.data(), n, records);
-  if (int rc = CheckSegments(st->segments, &err)) {
-    srt::SetError(err);
-    return rc;
-  }
-  std::vector<uint32_t> pos_rec(n);
-  std::vector<uint2> seg(records);
-  for (uint32_t r = 0; r < records; ++r) {
-    seg[r] = make_uint2(st->segments.first[r], st->segments.count[r]);
-    for (uint32_t k = 0; k < st->segments.count[r]; ++k) pos_rec[st->segments.first[r] + k] = r;
-  }
-  const size_t pair_bytes = 4 * sizeof(float4) * (size_t)n_pairs;
-  const size_t sched = sizeof(uint32_t) * ((size_t)n_pairs + kHeightBins + 1);
-  const size_t per_tri = sizeof(uint32_t) * (size_t)n;
-  const size_t zeroed = sizeof(uint32_t) * ZeroedWords(n, records);
-  const size_t seg_bytes = sizeof(uint2) * (size_t)records;
-  STAGE_HIP_OK(st->d_pairs.Alloc(pair_bytes));
-  STAGE_HIP_OK(st->d_triples.Alloc(sizeof(uint4) * (size_t)n));
-  STAGE_HIP_OK(st->d_schedule.Alloc(sched));
-  STAGE_HIP_OK(st->d_keys64_in.Alloc(2 * per_tri));
-  STAGE_HIP_OK(st->d_keys64.Alloc(2 * per_tri));
-  STAGE_HIP_OK(st->d_vals_in.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_keys.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_order.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_parent.Alloc(sizeof(uint32_t) * (2 * (size_t)n)));
-  STAGE_HIP_OK(st->d_height.Alloc(sizeof(uint32_t) * (size_t)n_pairs));
-  STAGE_HIP_OK(st->d_zeroed.Alloc(zeroed));
-  STAGE_HIP_OK(st->d_owner.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_pos_rec.Alloc(per_tri));
-  STAGE_HIP_OK(st->d_seg.Alloc(seg_bytes));
-  size_t temp = 0;
-  STAGE_HIP_OK(SortModels(*st, n, q->stream, nullptr, temp));  // the size only
-  st->temp_bytes = temp ? temp : 16;
-  STAGE_HIP_OK(st->d_temp.Alloc(st->temp_bytes));
-  STAGE_HIP_OK(hipMemcpyAsync(st->d_owner, owner.data(), per_tri, hipMemcpyHostToDevice, q->stream));
-  STAGE_HIP_OK(hipMemcpyAsync(st->d_pos_rec, pos_rec.data(), per_tri, hipMemcpyHostToDevice, q->stream));
-  STAGE_HIP_OK(hipMemcpyAsync(st->d_seg, seg.data(), seg_bytes, hipMemcpyHostToDevice, q->stream));
-  STAGE_HIP_OK(hipMemsetAsync(st->d_order, 0, per_tri, q->stream));
-  STAGE_HIP_OK(hipStreamSynchronize(q->stream));  // the host arrays go out of scope
-  st->bytes = pair_bytes + sizeof(uint4) * (size_t)n + sched + 4 * per_tri + 3 * per_tri + sizeof(uint32_t) * (2 * (size_t)n) +
-              sizeof(uint32_t) * (size_t)n_pairs + zeroed + 2 * per_tri + seg_bytes + st->temp_bytes;
-  q->rebuild = std::move(st);
-  return SRT_OK;
-}
-
-int RebuildModels(srt_query* q, const srt_vertex* verts_dev) {
-  STAGE_HIP_OK(hipSetDevice(q->device));
-  State& st = *q->rebuild;
-  const uint32_t n = q->n_tris;         // >= 2: two records or more, a triangle each at least
-  const uint32_t n_pairs = n - 1;       // the pair array's capacity
-  const uint32_t max_leaf = st.max_leaf;
-  const bool collapse = max_leaf > 1;
-  uint32_t karras_pairs = 0, root_leaf = 0;  // what the segments say before the device ran
-  SegmentShape(st.segments, max_leaf, &karras_pairs, &root_leaf);
-  const bool first_time = st.count == 0;
-  if (first_time) {
-    std::swap(st.d_pairs, q->d_pairs);
-    std::swap(st.d_triples, q->d_triples);
-    std::swap(st.d_schedule, q->d_schedule);
-  }
-  BParams bp;
-  std::memset(&bp, 0, sizeof bp);
-  bp.pairs = q->d_pairs;
-  bp.roots = q->d_roots;
-  bp.triples0 = st.d_triples;
-  bp.triples = q->d_triples;
-  bp.verts = reinterpret_cast<const float4*>(verts_dev);
-  bp.vals_in = st.d_vals_in;
-  bp.keys = st.d_keys;
-  bp.keys_out = st.d_keys;
-  bp.order = st.d_order;
-  bp.parent = st.d_parent;
-  bp.counts = st.d_zeroed;
-  bp.cursor = st.d_zeroed + kHeightBins;
-  bp.arrive = st.d_zeroed + 2 * kHeightBins;
-  bp.seg_box = st.d_zeroed + 2 * kHeightBins + n_pairs;
-  bp.height = st.d_height;
-  bp.schedule = q->d_schedule;
-  bp.n_verts = q->n_verts;
-  bp.n_tris = n;
-  bp.owner = st.d_owner;
-  bp.pos_rec = st.d_pos_rec;
-  bp.seg = st.d_seg;
-  bp.keys64_in = st.d_keys64_in;
-  bp.keys64 = st.d_keys64;
-  bp.n_records = st.records;
-  if (collapse) {
-    bp.split = st.d_split;
-    bp.flags = st.d_flags;
-    bp.rank = st.d_rank;
-    bp.leafsum = st.d_leafsum;
-    bp.max_leaf = max_leaf;
-  }
-  hipStream_t s = q->stream;
-  int launches = 0;
-#define REBUILD_LAUNCH(kernel, blocks)                                            \
-  do {                                                                            \
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, bp);             \
-    STAGE_HIP_OK(hipGetLastError());                                              \
-    ++launches;                                                                   \
-  } while (0)
-  STAGE_HIP_OK(hipMemsetAsync(st.d_zeroed, 0, sizeof(uint32_t) * ZeroedWords(n, st.records), s));
-  REBUILD_LAUNCH(seg_box_kernel, Blocks(n));
-  REBUILD_LAUNCH(keys_models_kernel, Blocks(n));
-  size_t temp = st.temp_bytes;
-  STAGE_HIP_OK(SortModels(st, n, s, st.d_temp, temp));
-  ++launches;  // (counted as one, as the one-record sort is)
-  REBUILD_LAUNCH(permute_models_kernel, Blocks(n));
-  if (collapse) {
-    REBUILD_LAUNCH(range_models_kernel, Blocks(n));
-    size_t scan_temp = st.scan_temp_bytes;
-    STAGE_HIP_OK(Scan(st.d_flags, st.d_rank, n, s, st.d_scan_temp, scan_temp));
-    ++launches;
-    REBUILD_LAUNCH(emit_models_kernel, Blocks(n));
-    REBUILD_LAUNCH((climb_kernel<true, true>), Blocks(n));
-    REBUILD_LAUNCH((schedule_kernel<true, true>), Blocks(n_pairs));
-    if (karras_pairs == 0)  // every record a leaf root: pair 0, which srt_query_copy_layout still copies, keeps nothing
-      STAGE_HIP_OK(hipMemsetAsync(q->d_pairs, 0, 4 * sizeof(float4), s));
-  } else {
-    REBUILD_LAUNCH(karras_models_kernel, Blocks(n));
-    REBUILD_LAUNCH((climb_kernel<false, true>), Blocks(n));
-    REBUILD_LAUNCH((schedule_kernel<false, true>), Blocks(n_pairs));
-  }
-#undef REBUILD_LAUNCH
-  STAGE_HIP_OK(hipMemcpyAsync(st.summary, st.d_zeroed, sizeof(uint32_t) * kHeightBins, hipMemcpyDeviceToHost, s));
-  if (collapse)
-    STAGE_HIP_OK(hipMemcpyAsync(st.leaf_summary, st.d_leafsum, sizeof st.leaf_summary, hipMemcpyDeviceToHost, s));
-  STAGE_HIP_OK(hipStreamSynchronize(s));  // the one synchronisation
-  if (first_time) {
-    st.d_pairs.Free();
-    st.d_schedule.Free();
-  }
-  const uint32_t m = collapse ? st.leaf_summary[0] : karras_pairs;
-  const uint32_t device_largest = collapse ? st.leaf_summary[1] : (karras_pairs ? 1u : 0u);
+  // without the emit kernel nothing was read back: m and the largest leaf are the segments' (a leaf root: 0 and n)
+  const uint32_t m = emitted ? st.leaf_summary[0] : karras_pairs;
+  const uint32_t device_largest = emitted ? st.leaf_summary[1] : (karras_pairs ? 1u : 0u);
   const uint32_t largest = device_largest > root_leaf ? device_largest : root_leaf;
-  const bool valid = !collapse || ModelsSummaryValid(m, device_largest, karras_pairs, max_leaf);
+  const bool valid = !emitted || ModelsSummaryValid(m, device_largest, karras_pairs, max_leaf);
   return Adopt(q, verts_dev, launches, m, collapse ? m : n_pairs, largest, valid);
 }
 
@@ -498,7 +417,6 @@ int srt_query_rebuild(srt_query* q, const srt_vertex* verts_dev, uint32_t n_vert
     srt::SetError(err);
     return rc;
   }
-  if (q->rebuild->models && q->rebuild->records > 1) return srt::rebuild::RebuildModels(q, verts_dev);
   return srt::rebuild::Rebuild(q, verts_dev);
 }
 
@@ -522,8 +440,7 @@ int srt_query_enable_rebuild_models(srt_query* q) {
     return rc;
   }
   if (q->rebuild) return SRT_OK;
-  if (q->n_bvhs > 1) return srt::rebuild::EnableModels(q);
-  // one record owns every triangle its root reaches, and the layout holds no other: srt_rebuild.h's object exactly
+  // (one record owns every triangle its root reaches, and the layout holds no other: srt_rebuild.h's object exactly)
   if (int rc = srt::rebuild::Enable(q)) return rc;
   q->rebuild->models = true;
   return SRT_OK;

@@ -1,29 +1,40 @@
-// rebuild.hpp -- the kernels of the device rebuild (include/srt_rebuild.h) over query_host.hpp's layout.  The
-// sort between keys_kernel and karras_kernel is hipcub's, and the boxes and triangle records are refit.hpp's
-// kernels over the schedule made here.
+// rebuild.hpp -- the kernels of the device rebuild (include/srt_rebuild.h, srt_rebuild_leaf.h, srt_rebuild_models.h) over
+// query_host.hpp's layout.  The sorts and the scan between them are hipcub's, and the boxes and triangle records are
+// refit.hpp's kernels over the schedule made here.
 //
-// box_partial_kernel / box_final_kernel: the scene box, a two-stage min / max reduction over the triangles.
-// keys_kernel: one lane per triangle in creation order; its Morton key and its own index as the sort's value.
-// karras_kernel: one lane per internal node; the .w fields of its pair's four records (the boxes are the
-//   refit's), the parents of its two children, and the roots' .w.
-// permute_kernel: one lane per position; the 16-B index triple of the triangle sorted there.
-// climb_kernel: one lane per leaf climbs towards the root.  At a node it exchanges its side's value into the
-//   node's arrival word: the first arriver reads 0 back and stops, the second reads the other side's value --
-//   the word itself carries what is handed over, nothing else written in this launch is read in it -- computes
-//   the pair's height and goes on.  No lane waits, spins or polls on another; the climb is bounded by the depth.
+// Record r owns the positions [s_r, s_r + n_r) of the sorted order, its segment, and the hierarchy is built per segment.
+// One record is the segment [0, n) known at compile time: every kernel that needs a position's segment is one body with
+// a template flag SEG, whose false instance loads nothing for it (segment_of).  Only the front differs in kind:
+//   one record: box_partial_kernel / box_final_kernel, the scene box by a two-stage min / max reduction, and 30-bit keys;
+//   several: seg_box_kernel, a box per record by atomics, and 64-bit (record, key) keys whose sort keeps the segments.
+//
+// keys_kernel: one lane per triangle in creation order; its Morton key in its record's box and its own index as the
+//   sort's value.
+// permute_kernel: one lane per position; the 16-B index triple of the triangle sorted there (SEG: and the sorted keys'
+//   low dwords, which the hierarchy reads).
+// karras_kernel (max_leaf 1): one lane per position.  The lane of a segment's first position writes the record's root
+//   (put_root: and the ghost root beside record 0) and marks the root's parent word kNoOwner; the lane of Karras node i
+//   writes the .w fields of pair i's four records (the boxes are the refit's) and the parents of its two children.  Pair
+//   and node indices are global -- record r's node k is pair s_r + k -- so the last index of every segment is an unused
+//   pair, kept zero.
+// range_kernel, hipcub's exclusive scan, emit_kernel (max_leaf > 1) stand in for karras_kernel, and the LEAF instances of
+//   climb_kernel and schedule_kernel work in rank space over the m pairs the scan counted -- m stays on the device
+//   (leafsum[0]) until the rebuild's one readback.
+//   range_kernel: one lane per position; its node's split (first, last, gamma) and whether it survives the collapse, and
+//     the position marked as owned by no pair.
+//   emit_kernel: the lane of a segment's first position writes the root, a leaf (s, c) or pair rank(s); the lane of a
+//     surviving node the .w fields of pair rank(i), the parents of its internal children in rank space, the owning pair
+//     of each leaf's first position, and the block's largest leaf count through one atomic max.  Only the first position
+//     of a leaf starts a climb; the marks of every other position stay.
+// root_leaf_kernel: one record of n <= max_leaf triangles; the leaf root (0, n).
+// climb_kernel: one lane per leaf climbs towards its record's root.  At a node it exchanges its side's value into the
+//   node's arrival word: the first arriver reads 0 back and stops, the second reads the other side's value -- the word
+//   itself carries what is handed over, nothing else written in this launch is read in it -- computes the pair's height
+//   and goes on; a root's parent word is kNoOwner, which is no pair.  No lane waits, spins or polls on another; the
+//   climb is bounded by the depth.
 // schedule_kernel: a counting sort of the pairs by height into the format refit.hpp reads (the order inside a
 //   height is free); a block takes its share of each height with one atomic per height.
 // remap_kernel: one lane per hit; the position srt_query_closest reported becomes the creation index.
-//
-// With max_leaf > 1 (include/srt_rebuild_leaf.h) range_kernel, hipcub's exclusive scan and emit_kernel stand in for
-// karras_kernel, and the LEAF instances of climb_kernel and schedule_kernel work in rank space over the m pairs
-// the scan counted -- m stays on the device (leafsum[0]) until the rebuild's one readback.
-// range_kernel: one lane per Karras node; its split (first, last, gamma) and whether it survives the collapse, and
-//   one lane per position marks it as owned by no pair.
-// emit_kernel: one lane per surviving node; the .w fields of pair rank(i), the parents of its internal children in
-//   rank space, the owning pair of each leaf's first position, and the block's largest leaf count through one
-//   atomic max.  Only the first position of a leaf starts a climb; the marks of every other position stay.
-// root_leaf_kernel: n <= max_leaf; the leaf root (0, n).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,23 +53,25 @@ constexpr uint32_t kMissTri = 0xFFFFFFFFu;
 
 struct BParams {
   float4* pairs;            // 4 float4 per sibling pair (n_tris - 1 of them)
-  float4* roots;            // 2 float4 per root record, two records
+  float4* roots;            // 2 float4 per root record, n_records + 1 records (the last is the ghost root)
   const uint4* triples0;    // creation order: v0, v1, v2, material
   uint4* triples;           // sorted order
   const float4* verts;      // 2 float4 per srt_vertex
-  float* box_partial;       // 8 floats per block of the first stage: lo xyz, -, hi xyz, -
-  float* box;               // 8 floats
-  uint32_t* keys_in;        // creation order
-  uint32_t* vals_in;
+  uint32_t* vals_in;        // creation order: the sort's values
   const uint32_t* keys;     // sorted
   const uint32_t* order;    // sorted: position -> creation index
-  uint32_t* parent;         // [0, n - 1): of internal nodes; [n - 1, 2n - 1): of leaf positions
+  uint32_t* parent;         // [0, n - 1): of pairs (kNoOwner: a record's root); [n - 1, 2n - 1): of leaf positions
   uint32_t* arrive;         // n - 1 arrival words, zero at launch
   uint32_t* height;         // n - 1
   uint32_t* counts;         // kHeightBins pairs per height, zero at launch
   uint32_t* cursor;         // kHeightBins, zero at launch
   uint32_t* schedule;       // n - 1 pair indices by height
-  uint32_t n_verts, n_tris, box_blocks;
+  uint32_t n_verts, n_tris, n_records;
+  // one record only (null / 0 otherwise)
+  float* box_partial;       // 8 floats per block of the first stage: lo xyz, -, hi xyz, -
+  float* box;               // 8 floats
+  uint32_t* keys_in;        // creation order
+  uint32_t box_blocks;
   // max_leaf > 1 only (null / 0 otherwise); then `parent` is [0, n - 1): of pairs, by rank; [n - 1, 2n - 1): the pair
   // that owns the leaf starting at the position, or kNoOwner
   uint4* split;             // n - 1: first, last, gamma, survives
@@ -66,8 +79,7 @@ struct BParams {
   const uint32_t* rank;     // n: the exclusive sum of flags; rank[n - 1] == m
   uint32_t* leafsum;        // m, the largest leaf count
   uint32_t max_leaf;
-  // include/srt_rebuild_models.h, two records or more only (null / 0 otherwise); `keys` is then what permute_models_kernel
-  // unpacked, and pair indices are global: record r's Karras node k is pair s_r + k
+  // two records or more only (null otherwise); `keys` is then what permute_kernel unpacked
   const uint32_t* owner;    // n: creation index -> record
   const uint32_t* pos_rec;  // n: position -> record (the segments never move)
   const uint2* seg;         // per record: s_r, n_r
@@ -75,10 +87,20 @@ struct BParams {
   uint64_t* keys64_in;      // creation order: (record << 32) | morton
   const uint64_t* keys64;   // sorted
   uint32_t* keys_out;       // sorted: the low dwords (what `keys` points to)
-  uint32_t n_records;
 };
 
 constexpr uint32_t kNoOwner = 0xFFFFFFFFu;  // (not below any pair count: such a position starts no climb)
+
+// A pair (or Karras node) index is < n - 1 and a position is < n by construction; the clamps keep every load and store
+// inside its array whatever the device arrays hold (n >= 2).
+__device__ __forceinline__ uint32_t pair_index(const BParams& bp, uint32_t x) { return x < bp.n_tris - 1u ? x : bp.n_tris - 2u; }
+
+__device__ __forceinline__ uint32_t leaf_pos(const BParams& bp, uint32_t x) { return x < bp.n_tris ? x : bp.n_tris - 1u; }
+
+// The word of `parent` that belongs to a child reference: of a pair, or of the leaf that starts at a position.
+__device__ __forceinline__ uint32_t parent_slot(const BParams& bp, uint32_t index, bool leaf) {
+  return leaf ? bp.n_tris - 1u + leaf_pos(bp, index) : pair_index(bp, index);
+}
 
 struct Span3 {
   float lo[3], hi[3];
@@ -144,6 +166,7 @@ __device__ __forceinline__ Span3 block_span(Span3 s, bool have, const Span3& neu
   return s;
 }
 
+// -- the front: the box of every record, the keys --------------------------------------------------------------------------
 // Stage 1: block b folds triangles b * 256 + lane, + box_blocks * 256, ...; triangle 0's span is the neutral
 // element (it is part of the result anyway), so no infinity enters.
 __global__ __launch_bounds__(256) void box_partial_kernel(BParams bp) {
@@ -185,200 +208,10 @@ __global__ __launch_bounds__(256) void box_final_kernel(BParams bp) {
     }
 }
 
-__global__ __launch_bounds__(256) void keys_kernel(BParams bp) {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= bp.n_tris) return;
-  const Span3 s = tri_span(bp, t);
-  uint32_t q[3];
-  for (int k = 0; k < 3; ++k) q[k] = Cell(bp.box[k], bp.box[4 + k], s.lo[k], s.hi[k]);
-  bp.keys_in[t] = Morton(q[0], q[1], q[2]);
-  bp.vals_in[t] = t;
-}
-
-// One record's .w fields; the bounds are the refit's to write.
-__device__ __forceinline__ void put_child(float4* rec, const Child& c) {
-  rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c.index));
-  rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c.leaf ? 1u : 0u));
-}
-
-__global__ __launch_bounds__(256) void karras_kernel(BParams bp) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t n = bp.n_tris;  // >= 2
-  if (i == 0) {  // both root records (the BVH record and the ghost root) reference pair 0
-    const Child root{0u, false};
-    put_child(bp.roots, root);
-    put_child(bp.roots + 2, root);
-  }
-  if (i + 1 >= n) return;
-  Child l, r;
-  KarrasNode(bp.keys, n, i, &l, &r);
-  float4* rec = bp.pairs + 4 * (size_t)i;
-  put_child(rec, l);
-  put_child(rec + 2, r);
-  // a child index is < n - 1 (internal) or < n (leaf) by construction; the clamp keeps a store inside the array
-  const uint32_t li = l.leaf ? n - 1 + (l.index < n ? l.index : n - 1) : (l.index < n - 1 ? l.index : n - 2);
-  const uint32_t ri = r.leaf ? n - 1 + (r.index < n ? r.index : n - 1) : (r.index < n - 1 ? r.index : n - 2);
-  bp.parent[li] = i;
-  bp.parent[ri] = i;
-}
-
-__global__ __launch_bounds__(256) void permute_kernel(BParams bp) {
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= bp.n_tris) return;
-  const uint32_t src = bp.order[p];
-  bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];  // (a whole record: one 16-B load, one 16-B store)
-}
-
-// The pairs of the tree being built: n - 1, or with LEAF the m the scan counted (never more than n - 1).
-template <bool LEAF>
-__device__ __forceinline__ uint32_t pair_count(const BParams& bp) {
-  if (!LEAF) return bp.n_tris - 1u;
-  const uint32_t m = bp.leafsum[0];
-  return m < bp.n_tris - 1u ? m : bp.n_tris - 1u;
-}
-
-// SEG (include/srt_rebuild_models.h): the climb ends at a pair without a parent -- a record's root, whose parent word
-// is kNoOwner -- not at pair 0.
-template <bool LEAF, bool SEG = false>
-__global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
-  __shared__ uint32_t bins[kHeightBins];
-  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
-  __syncthreads();
-  const uint32_t n = bp.n_tris;  // >= 2
-  const uint32_t n_pairs = pair_count<LEAF>(bp);
-  const uint32_t leaf = blockIdx.x * kBlock + threadIdx.x;  // (LEAF: a position; the first of a leaf has an owner)
-  if (leaf < n) {
-    uint32_t p = bp.parent[n - 1 + leaf];
-    uint32_t val = 0u;  // of a child: 0 for a leaf, its pair's height + 1 for an internal node
-    for (int step = 0; step < kHeightBins && p < n_pairs; ++step) {
-      const uint32_t old = __hip_atomic_exchange(bp.arrive + p, val + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (old == 0u) break;  // the first to arrive: the other side's lane carries on from here
-      uint32_t h = old - 1u > val ? old - 1u : val;
-      h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;  // (the depth bound keeps it below)
-      bp.height[p] = h;
-      atomicAdd(&bins[h], 1u);
-      if (!SEG && p == 0u) break;  // the root
-      val = h + 1u;
-      p = bp.parent[p];
-    }
-  }
-  __syncthreads();  // (every lane arrives: the climb above waits for nothing)
-  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) atomicAdd(bp.counts + threadIdx.x, bins[threadIdx.x]);
-}
-
-// SEG without LEAF: the pair array has unused slots (index e_r of every record); a pair exists iff both its children
-// arrived, which left its arrival word non-zero.
-template <bool LEAF, bool SEG = false>
-__global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
-  __shared__ uint32_t bins[kHeightBins], base[kHeightBins];
-  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
-  __syncthreads();
-  const uint32_t n_pairs = pair_count<LEAF>(bp);
-  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  uint32_t h = 0u, rank = 0u;
-  const bool exists = p < n_pairs && (LEAF || !SEG || bp.arrive[p] != 0u);
-  if (exists) {
-    h = bp.height[p];
-    h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;
-    rank = atomicAdd(&bins[h], 1u);
-  }
-  __syncthreads();
-  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) {
-    uint32_t first = 0u;  // of this height: the pairs of the heights under it
-    for (uint32_t k = 0; k < threadIdx.x; ++k) first += bp.counts[k];
-    base[threadIdx.x] = first + atomicAdd(bp.cursor + threadIdx.x, bins[threadIdx.x]);
-  }
-  __syncthreads();
-  if (exists) {
-    const uint32_t at = base[h] + rank;
-    if (at < n_pairs) bp.schedule[at] = p;
-  }
-}
-
-// -- max_leaf > 1 ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void range_kernel(BParams bp) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t n = bp.n_tris;  // > max_leaf >= 2
-  if (i >= n) return;
-  if (i == 0) bp.leafsum[1] = 0u;  // the emit kernel's atomic max starts here
-  bp.parent[n - 1 + i] = kNoOwner;
-  uint32_t survives = 0u;
-  if (i + 1 < n) {
-    const Split sp = KarrasSplit(bp.keys, n, i);
-    survives = Survives(sp, bp.max_leaf) ? 1u : 0u;
-    bp.split[i] = make_uint4((uint32_t)sp.first, (uint32_t)sp.last, (uint32_t)sp.gamma, survives);
-  }
-  bp.flags[i] = survives;
-}
-
-// One slot of pair r; an index is < n - 1 (a node) or < n (a position) by construction, the clamps keep every store
-// inside its array.
-__device__ __forceinline__ uint32_t emit_slot(const BParams& bp, float4* rec, const Slot& s, uint32_t r) {
-  const uint32_t n = bp.n_tris;
-  if (s.count > 0u) {
-    const uint32_t pos = s.index < n ? s.index : n - 1u;
-    rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(pos));
-    rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(s.count));
-    bp.parent[n - 1u + pos] = r;
-    return s.count;
-  }
-  uint32_t c = bp.rank[s.index < n - 1u ? s.index : n - 2u];
-  c = c < n - 1u ? c : n - 2u;
-  rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(c));
-  rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
-  bp.parent[c] = r;
-  return 0u;
-}
-
-__global__ __launch_bounds__(256) void emit_kernel(BParams bp) {
-  __shared__ uint32_t largest;
-  if (threadIdx.x == 0) largest = 0u;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t n = bp.n_tris;
-  if (i == 0) {  // both root records reference pair 0 (node 0 survives: n > max_leaf), and m for the kernels after
-    const Child root{0u, false};
-    put_child(bp.roots, root);
-    put_child(bp.roots + 2, root);
-    bp.leafsum[0] = bp.rank[n - 1u];
-  }
-  if (i + 1 < n) {
-    const uint4 sp4 = bp.split[i];
-    if (sp4.w != 0u) {
-      Split sp;
-      sp.first = sp4.x;
-      sp.last = sp4.y;
-      sp.gamma = sp4.z;
-      uint32_t r = bp.rank[i];
-      r = r < n - 1u ? r : n - 2u;
-      float4* rec = bp.pairs + 4 * (size_t)r;
-      const uint32_t a = emit_slot(bp, rec, LeftSlot(sp, bp.max_leaf), r);
-      const uint32_t b = emit_slot(bp, rec + 2, RightSlot(sp, bp.max_leaf), r);
-      if ((a > b ? a : b) > 0u) atomicMax(&largest, a > b ? a : b);
-    }
-  }
-  __syncthreads();  // (every lane arrives)
-  if (threadIdx.x == 0 && largest != 0u) atomicMax(bp.leafsum + 1, largest);
-}
-
-__global__ __launch_bounds__(256) void root_leaf_kernel(BParams bp) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  for (int r = 0; r < 2; ++r) {  // the BVH record and the ghost root
-    bp.roots[2 * r] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
-    bp.roots[2 * r + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(bp.n_tris));
-  }
-}
-
-// -- two records or more (include/srt_rebuild_models.h) -------------------------------------------------------------------
 // seg_box_kernel: one lane per triangle; the box of its owner.  Floats go through the order-preserving map to uint32, the
 //   lower bounds complemented, so every bound is an atomic max over words zeroed at launch: min and max of values are
 //   exact and commute, no neutral element and no infinity is needed, and a record's box holds its own triangles only.  A
 //   block whose triangles all have one owner folds in the block first and issues six atomics.
-// keys_models_kernel: the key in the owner's box, the owner in the high dword.
-// permute_models_kernel: permute_kernel, and the sorted keys' low dwords for the hierarchy.
-// karras_models_kernel / range_models_kernel / emit_models_kernel: one lane per position; its segment from pos_rec and
-//   seg, the node by SegmentSplit, and the root record of the segment (and the ghost root for record 0) by the lane of the
-//   segment's first position.  A root pair's parent word is kNoOwner.
 __device__ __forceinline__ uint32_t ordered(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -418,86 +251,110 @@ __global__ __launch_bounds__(256) void seg_box_kernel(BParams bp) {
   }
 }
 
-__global__ __launch_bounds__(256) void keys_models_kernel(BParams bp) {
+// SEG: the key in the owner's box, the owner in the high dword.
+template <bool SEG>
+__global__ __launch_bounds__(256) void keys_kernel(BParams bp) {
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= bp.n_tris) return;
-  const uint32_t r = owner_of(bp, t);
-  const uint32_t* box = bp.seg_box + 8 * (size_t)r;
+  const uint32_t r = SEG ? owner_of(bp, t) : 0u;
   const Span3 s = tri_span(bp, t);
   uint32_t q[3];
-  for (int k = 0; k < 3; ++k) q[k] = Cell(unordered(~box[k]), unordered(box[4 + k]), s.lo[k], s.hi[k]);
-  bp.keys64_in[t] = RecordKey(r, Morton(q[0], q[1], q[2]));
+  for (int k = 0; k < 3; ++k) {
+    float lo, hi;
+    if (SEG) {
+      const uint32_t* e = bp.seg_box + 8 * (size_t)r;
+      lo = unordered(~e[k]);
+      hi = unordered(e[4 + k]);
+    } else {
+      lo = bp.box[k];
+      hi = bp.box[4 + k];
+    }
+    q[k] = Cell(lo, hi, s.lo[k], s.hi[k]);
+  }
+  const uint32_t key = Morton(q[0], q[1], q[2]);
+  if (SEG) bp.keys64_in[t] = RecordKey(r, key);
+  else bp.keys_in[t] = key;
   bp.vals_in[t] = t;
 }
 
-__global__ __launch_bounds__(256) void permute_models_kernel(BParams bp) {
+template <bool SEG>
+__global__ __launch_bounds__(256) void permute_kernel(BParams bp) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
   if (p >= bp.n_tris) return;
-  bp.keys_out[p] = (uint32_t)bp.keys64[p];
+  if (SEG) bp.keys_out[p] = (uint32_t)bp.keys64[p];
   const uint32_t src = bp.order[p];
-  bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];
+  bp.triples[p] = bp.triples0[src < bp.n_tris ? src : 0u];  // (a whole record: one 16-B load, one 16-B store)
 }
 
-// The segment of position i (< n): s <= i < s + c <= n whatever the device arrays hold.
+// -- the hierarchy --------------------------------------------------------------------------------------------------------
+// The segment of position i (< n): s <= i < s + c <= n whatever the device arrays hold.  Without SEG it is [0, n) of
+// record 0, and nothing is loaded.
 struct Segment {
   uint32_t r, s, c;
 };
 
+template <bool SEG>
 __device__ __forceinline__ Segment segment_of(const BParams& bp, uint32_t i) {
-  Segment g;
-  g.r = bp.pos_rec[i];
-  g.r = g.r < bp.n_records ? g.r : bp.n_records - 1u;
-  const uint2 sc = bp.seg[g.r];
-  g.s = sc.x <= i ? sc.x : i;
-  g.c = sc.y <= bp.n_tris - g.s ? sc.y : bp.n_tris - g.s;
-  g.c = i - g.s < g.c ? g.c : i - g.s + 1u;
+  Segment g{0u, 0u, bp.n_tris};
+  if (SEG) {
+    g.r = bp.pos_rec[i];
+    g.r = g.r < bp.n_records ? g.r : bp.n_records - 1u;
+    const uint2 sc = bp.seg[g.r];
+    g.s = sc.x <= i ? sc.x : i;
+    g.c = sc.y <= bp.n_tris - g.s ? sc.y : bp.n_tris - g.s;
+    g.c = i - g.s < g.c ? g.c : i - g.s + 1u;
+  }
   return g;
 }
 
-// Root record r, and the ghost root (record n_records) beside record 0: `ref` is a pair index (count 0) or a position.
-__device__ __forceinline__ void put_root(const BParams& bp, uint32_t r, uint32_t ref, uint32_t count) {
-  for (uint32_t at = r;; at = bp.n_records) {
-    bp.roots[2 * (size_t)at] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(ref));
-    bp.roots[2 * (size_t)at + 1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(count));
-    if (r != 0u || at == bp.n_records) break;
-  }
+// One reference, the .w fields of a record of two float4 (the bounds are the refit's to write): a pair index and 0, or
+// a leaf's first position and its count.
+__device__ __forceinline__ void put_ref(float4* rec, uint32_t ref, uint32_t count) {
+  rec[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(ref));
+  rec[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(count));
 }
 
-__global__ __launch_bounds__(256) void karras_models_kernel(BParams bp) {
+// Root record r, and the ghost root (record n_records) beside record 0.
+__device__ __forceinline__ void put_root(const BParams& bp, uint32_t r, uint32_t ref, uint32_t count) {
+  put_ref(bp.roots + 2 * (size_t)r, ref, count);
+  if (r == 0u) put_ref(bp.roots + 2 * (size_t)bp.n_records, ref, count);
+}
+
+template <bool SEG>
+__global__ __launch_bounds__(256) void karras_kernel(BParams bp) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t n = bp.n_tris;  // >= 2
   if (i >= n) return;
-  const Segment g = segment_of(bp, i);
-  if (i == g.s) {
+  const Segment g = segment_of<SEG>(bp, i);
+  if (i == g.s) {  // a root pair climbs no further; a leaf root's position starts no climb
     const Slot root = SegmentRoot(g.s, g.c, 1u);
     put_root(bp, g.r, root.index, root.count);
-    if (root.count == 0u) bp.parent[i < n - 1u ? i : n - 2u] = kNoOwner;  // (c >= 2: i <= n - 2)
-    else bp.parent[n - 1u + i] = kNoOwner;                                // a leaf root: its position starts no climb
+    bp.parent[parent_slot(bp, i, root.count > 0u)] = kNoOwner;
   }
   if (i + 1u >= n) return;  // (no pair slot n - 1)
   float4* rec = bp.pairs + 4 * (size_t)i;
-  if (i - g.s + 1u >= g.c) {  // index e_r: unused, kept zero
+  if (i - g.s + 1u >= g.c) {  // the last index of a segment: unused, kept zero
     for (int k = 0; k < 4; ++k) rec[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return;
   }
   const Split sp = SegmentSplit(bp.keys, g.s, g.c, i);
   const Child l{(uint32_t)sp.gamma, sp.first == sp.gamma}, r{(uint32_t)(sp.gamma + 1), sp.last == sp.gamma + 1};
-  put_child(rec, l);
-  put_child(rec + 2, r);
-  const uint32_t li = l.leaf ? n - 1 + (l.index < n ? l.index : n - 1) : (l.index < n - 1 ? l.index : n - 2);
-  const uint32_t ri = r.leaf ? n - 1 + (r.index < n ? r.index : n - 1) : (r.index < n - 1 ? r.index : n - 2);
-  bp.parent[li] = i;
-  bp.parent[ri] = i;
+  put_ref(rec, l.index, l.leaf ? 1u : 0u);
+  put_ref(rec + 2, r.index, r.leaf ? 1u : 0u);
+  bp.parent[parent_slot(bp, l.index, l.leaf)] = i;
+  bp.parent[parent_slot(bp, r.index, r.leaf)] = i;
 }
 
-__global__ __launch_bounds__(256) void range_models_kernel(BParams bp) {
+// -- max_leaf > 1 ------------------------------------------------------------------------------------------------------
+template <bool SEG>
+__global__ __launch_bounds__(256) void range_kernel(BParams bp) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t n = bp.n_tris;  // >= 2
   if (i >= n) return;
-  if (i == 0) bp.leafsum[1] = 0u;
+  if (i == 0) bp.leafsum[1] = 0u;  // the emit kernel's atomic max starts here
   bp.parent[n - 1 + i] = kNoOwner;
-  const Segment g = segment_of(bp, i);
-  uint4 out = make_uint4(0u, 0u, 0u, 0u);
+  const Segment g = segment_of<SEG>(bp, i);
+  uint4 out = make_uint4(0u, 0u, 0u, 0u);  // a leaf root's segment has no node, nor has a segment's last index
   if (g.c > bp.max_leaf && i - g.s + 1u < g.c) {
     const Split sp = SegmentSplit(bp.keys, g.s, g.c, i);
     out = make_uint4((uint32_t)sp.first, (uint32_t)sp.last, (uint32_t)sp.gamma, Survives(sp, bp.max_leaf) ? 1u : 0u);
@@ -506,22 +363,31 @@ __global__ __launch_bounds__(256) void range_models_kernel(BParams bp) {
   bp.flags[i] = out.w;
 }
 
-__global__ __launch_bounds__(256) void emit_models_kernel(BParams bp) {
+// One slot of pair r.
+__device__ __forceinline__ uint32_t emit_slot(const BParams& bp, float4* rec, const Slot& s, uint32_t r) {
+  const bool leaf = s.count > 0u;
+  const uint32_t ref = leaf ? leaf_pos(bp, s.index) : pair_index(bp, bp.rank[pair_index(bp, s.index)]);
+  put_ref(rec, ref, s.count);
+  bp.parent[parent_slot(bp, ref, leaf)] = r;
+  return s.count;
+}
+
+template <bool SEG>
+__global__ __launch_bounds__(256) void emit_kernel(BParams bp) {
   __shared__ uint32_t largest;
   if (threadIdx.x == 0) largest = 0u;
   __syncthreads();
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t n = bp.n_tris;
-  if (i == 0) bp.leafsum[0] = bp.rank[n - 1u];
+  if (i == 0) bp.leafsum[0] = bp.rank[n - 1u];  // m for the kernels after
   if (i < n) {
-    const Segment g = segment_of(bp, i);
+    const Segment g = segment_of<SEG>(bp, i);
     if (i == g.s) {
       const Slot root = SegmentRoot(g.s, g.c, bp.max_leaf);
       if (root.count > 0u) {
         put_root(bp, g.r, root.index, root.count);
-      } else {  // node s_r survives: c > max_leaf
-        uint32_t rr = bp.rank[i < n - 1u ? i : n - 2u];
-        rr = rr < n - 1u ? rr : n - 2u;
+      } else {  // node s survives: c > max_leaf
+        const uint32_t rr = pair_index(bp, bp.rank[pair_index(bp, i)]);
         put_root(bp, g.r, rr, 0u);
         bp.parent[rr] = kNoOwner;
       }
@@ -534,8 +400,7 @@ __global__ __launch_bounds__(256) void emit_models_kernel(BParams bp) {
       sp.first = sp4.x;
       sp.last = sp4.y;
       sp.gamma = sp4.z;
-      uint32_t r = bp.rank[i];
-      r = r < n - 1u ? r : n - 2u;
+      const uint32_t r = pair_index(bp, bp.rank[i]);
       float4* rec = bp.pairs + 4 * (size_t)r;
       const uint32_t a = emit_slot(bp, rec, LeftSlot(sp, bp.max_leaf), r);
       const uint32_t b = emit_slot(bp, rec + 2, RightSlot(sp, bp.max_leaf), r);
@@ -544,6 +409,74 @@ __global__ __launch_bounds__(256) void emit_models_kernel(BParams bp) {
   }
   __syncthreads();  // (every lane arrives)
   if (threadIdx.x == 0 && largest != 0u) atomicMax(bp.leafsum + 1, largest);
+}
+
+__global__ __launch_bounds__(256) void root_leaf_kernel(BParams bp) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) put_root(bp, 0u, 0u, bp.n_tris);
+}
+
+// -- the heights and the schedule ------------------------------------------------------------------------------------------
+// The pairs of the tree being built: n - 1, or with LEAF the m the scan counted (never more than n - 1).
+template <bool LEAF>
+__device__ __forceinline__ uint32_t pair_count(const BParams& bp) {
+  if (!LEAF) return bp.n_tris - 1u;
+  const uint32_t m = bp.leafsum[0];
+  return m < bp.n_tris - 1u ? m : bp.n_tris - 1u;
+}
+
+template <bool LEAF>
+__global__ __launch_bounds__(256) void climb_kernel(BParams bp) {
+  __shared__ uint32_t bins[kHeightBins];
+  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t n = bp.n_tris;  // >= 2
+  const uint32_t n_pairs = pair_count<LEAF>(bp);
+  const uint32_t leaf = blockIdx.x * kBlock + threadIdx.x;  // (LEAF: a position; the first of a leaf has an owner)
+  if (leaf < n) {
+    uint32_t p = bp.parent[n - 1 + leaf];
+    uint32_t val = 0u;  // of a child: 0 for a leaf, its pair's height + 1 for an internal node
+    for (int step = 0; step < kHeightBins && p < n_pairs; ++step) {  // (a root's parent is kNoOwner)
+      const uint32_t old = __hip_atomic_exchange(bp.arrive + p, val + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old == 0u) break;  // the first to arrive: the other side's lane carries on from here
+      uint32_t h = old - 1u > val ? old - 1u : val;
+      h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;  // (the depth bound keeps it below)
+      bp.height[p] = h;
+      atomicAdd(&bins[h], 1u);
+      val = h + 1u;
+      p = bp.parent[p];
+    }
+  }
+  __syncthreads();  // (every lane arrives: the climb above waits for nothing)
+  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) atomicAdd(bp.counts + threadIdx.x, bins[threadIdx.x]);
+}
+
+// SEG without LEAF: the pair array has unused slots (the last index of every segment); a pair exists iff both its
+// children arrived, which left its arrival word non-zero.
+template <bool LEAF, bool SEG>
+__global__ __launch_bounds__(256) void schedule_kernel(BParams bp) {
+  __shared__ uint32_t bins[kHeightBins], base[kHeightBins];
+  if (threadIdx.x < kHeightBins) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t n_pairs = pair_count<LEAF>(bp);
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t h = 0u, rank = 0u;
+  const bool exists = p < n_pairs && (LEAF || !SEG || bp.arrive[p] != 0u);
+  if (exists) {
+    h = bp.height[p];
+    h = h < (uint32_t)kHeightBins ? h : (uint32_t)kHeightBins - 1u;
+    rank = atomicAdd(&bins[h], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < kHeightBins && bins[threadIdx.x] != 0u) {
+    uint32_t first = 0u;  // of this height: the pairs of the heights under it
+    for (uint32_t k = 0; k < threadIdx.x; ++k) first += bp.counts[k];
+    base[threadIdx.x] = first + atomicAdd(bp.cursor + threadIdx.x, bins[threadIdx.x]);
+  }
+  __syncthreads();
+  if (exists) {
+    const uint32_t at = base[h] + rank;
+    if (at < n_pairs) bp.schedule[at] = p;
+  }
 }
 
 // hits: 2 uint4 per srt_hit; the first dword is the triangle.

@@ -25,6 +25,65 @@ void Span(const srt_triangle& t, const srt_vertex* verts, uint32_t n_verts, int 
   *mx = refit::FoldMax(refit::FoldMax(a, b), c);
 }
 
+// Rule 2: the key of a triangle in the box [lo, hi] of its record
+uint32_t Key(const srt_triangle& t, const srt_vertex* verts, uint32_t n_verts, const float* lo, const float* hi) {
+  uint32_t q[3];
+  for (int k = 0; k < 3; ++k) {
+    float mn, mx;
+    Span(t, verts, n_verts, k, &mn, &mx);
+    q[k] = Cell(lo[k], hi[k], mn, mx);
+  }
+  return Morton(q[0], q[1], q[2]);
+}
+
+// Rule 3: the stable order of the input indices by key (a Morton key, or a (record, key)), the triangles and the order
+// out; returns the sorted keys' low dwords, which rule 4 reads.
+template <class K>
+std::vector<uint32_t> SortByKey(const std::vector<K>& keys, const srt_triangle* tris, srt_triangle* tris_out, uint32_t* order_out) {
+  const uint32_t n = (uint32_t)keys.size();
+  std::vector<uint32_t> order(n), sorted(n);
+  std::iota(order.begin(), order.end(), 0u);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+  for (uint32_t p = 0; p < n; ++p) {
+    sorted[p] = (uint32_t)keys[order[p]];
+    tris_out[p] = tris[order[p]];
+    order_out[p] = order[p];
+  }
+  return sorted;
+}
+
+// Rule 4 with 4a-4c over the segment [s, s + c) of the sorted keys (c >= 1), a block of nodes from `base`: the block's
+// root, then -- every node's split, the survivors' ranks by increasing index -- the children of the k-th survivor at block
+// nodes 2k + 1 and 2k + 2.  With max_leaf == 1 every internal node survives and its rank is its local index.  Returns the
+// block's node count, 2m + 1.
+size_t PutSegment(const uint32_t* sorted, uint32_t s, uint32_t c, uint32_t max_leaf, size_t base, srt_bvh_node* nodes_out) {
+  std::vector<Split> split;
+  std::vector<uint32_t> rank;
+  auto put = [&](size_t at, const Slot& slot) {
+    nodes_out[at] = srt_bvh_node{};
+    nodes_out[at].first_child_or_prim_index = slot.count ? slot.index : (uint32_t)(base + 2 * (size_t)rank[slot.index - s] + 1);
+    nodes_out[at].prim_count = slot.count;
+  };
+  const Slot root = SegmentRoot(s, c, max_leaf);
+  uint32_t m = 0;
+  if (root.count == 0) {
+    split.resize(c - 1);
+    rank.resize(c - 1);
+    for (uint32_t k = 0; k + 1 < c; ++k) {
+      split[k] = SegmentSplit(sorted, s, c, s + k);
+      rank[k] = m;
+      if (Survives(split[k], max_leaf)) ++m;
+    }
+  }
+  put(base, root);
+  for (uint32_t k = 0; k < split.size(); ++k) {
+    if (!Survives(split[k], max_leaf)) continue;
+    put(base + 2 * (size_t)rank[k] + 1, LeftSlot(split[k], max_leaf));
+    put(base + 2 * (size_t)rank[k] + 2, RightSlot(split[k], max_leaf));
+  }
+  return 2 * (size_t)m + 1;
+}
+
 }  // namespace
 
 void SceneBox(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, float lo[3], float hi[3]) {
@@ -42,15 +101,7 @@ void SceneBox(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts
 void Keys(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, uint32_t* keys) {
   float lo[3], hi[3];
   SceneBox(tris, n_tris, verts, n_verts, lo, hi);
-  for (uint32_t t = 0; t < n_tris; ++t) {
-    uint32_t q[3];
-    for (int k = 0; k < 3; ++k) {
-      float mn, mx;
-      Span(tris[t], verts, n_verts, k, &mn, &mx);
-      q[k] = Cell(lo[k], hi[k], mn, mx);
-    }
-    keys[t] = Morton(q[0], q[1], q[2]);
-  }
+  for (uint32_t t = 0; t < n_tris; ++t) keys[t] = Key(tris[t], verts, n_verts, lo, hi);
 }
 
 int DepthBound(uint32_t n_tris) {
@@ -74,45 +125,11 @@ int BuildLBVHLeaf(const srt_triangle* tris, uint32_t n_tris, const srt_vertex* v
   for (uint32_t i = 0; i < n_verts; ++i)
     for (int k = 0; k < 3; ++k)
       if (!std::isfinite(verts[i].vertex[k])) return Fail(err, "srt_bvh_build_lbvh: a vertex position is not finite");
-  // rules 1-3: keys in input order, then a stable sort of the input indices
-  std::vector<uint32_t> keys(n_tris), order(n_tris);
+  // rules 1-3: keys in the scene box, in input order, then the stable order; rule 4: one segment, its block at node 0
+  std::vector<uint32_t> keys(n_tris);
   Keys(tris, n_tris, verts, n_verts, keys.data());
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
-  std::vector<uint32_t> sorted(n_tris);
-  for (uint32_t p = 0; p < n_tris; ++p) {
-    sorted[p] = keys[order[p]];
-    tris_out[p] = tris[order[p]];
-    order_out[p] = order[p];
-  }
-  // rule 4 with 4a-4c: every node's split, the survivors' ranks by increasing Karras index, then the children of
-  // survivor i at nodes 2 rank(i) + 1 and 2 rank(i) + 2; node 0 is the root.  With max_leaf == 1 every internal node
-  // survives and rank(i) == i.
-  const uint32_t n_internal = n_tris - 1;
-  std::vector<Split> split(n_internal);
-  std::vector<uint32_t> rank(n_internal);
-  uint32_t m = 0;
-  for (uint32_t i = 0; i < n_internal; ++i) {
-    split[i] = KarrasSplit(sorted.data(), n_tris, i);
-    rank[i] = m;
-    if (Survives(split[i], max_leaf)) ++m;
-  }
-  const size_t n_nodes = 2 * (size_t)m + 1;
-  for (size_t i = 0; i < n_nodes; ++i) nodes_out[i] = srt_bvh_node{};
-  auto put = [&](size_t at, const Slot& s) {
-    nodes_out[at].first_child_or_prim_index = s.count ? s.index : 2 * rank[s.index] + 1;
-    nodes_out[at].prim_count = s.count;
-  };
-  if (n_tris <= max_leaf) {
-    put(0, Slot{0, n_tris});
-  } else {
-    put(0, Slot{0, 0});
-    for (uint32_t i = 0; i < n_internal; ++i) {
-      if (!Survives(split[i], max_leaf)) continue;
-      put(2 * (size_t)rank[i] + 1, LeftSlot(split[i], max_leaf));
-      put(2 * (size_t)rank[i] + 2, RightSlot(split[i], max_leaf));
-    }
-  }
+  const std::vector<uint32_t> sorted = SortByKey(keys, tris, tris_out, order_out);
+  const size_t n_nodes = PutSegment(sorted.data(), 0, n_tris, max_leaf, 0, nodes_out);
   *n_nodes_out = (uint32_t)n_nodes;
   // rule 5: srt_refit.h's fold on the new topology (which also walks the tree: a malformed one fails here)
   srt_bvh_record rec{};
@@ -297,57 +314,16 @@ int BuildLBVHModels(const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_n
     have[r] = 1;
   }
   std::vector<uint64_t> keys(n_tris);
-  for (uint32_t t = 0; t < n_tris; ++t) {
-    const uint32_t r = owner[t];
-    uint32_t q[3];
-    for (int k = 0; k < 3; ++k) {
-      float mn, mx;
-      Span(tris[t], verts, n_verts, k, &mn, &mx);
-      q[k] = Cell(lo[3 * (size_t)r + k], hi[3 * (size_t)r + k], mn, mx);
-    }
-    keys[t] = RecordKey(r, Morton(q[0], q[1], q[2]));
-  }
-  std::vector<uint32_t> order(n_tris), sorted(n_tris);
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
-  for (uint32_t p = 0; p < n_tris; ++p) {
-    sorted[p] = (uint32_t)keys[order[p]];
-    tris_out[p] = tris[order[p]];
-    order_out[p] = order[p];
-  }
-  // the hierarchy per segment, a block of nodes per record: the block's root, then the children of its pair k (the
-  // k-th survivor of the segment by increasing index) at block nodes 2k + 1 and 2k + 2
+  for (uint32_t t = 0; t < n_tris; ++t)
+    keys[t] = RecordKey(owner[t], Key(tris[t], verts, n_verts, &lo[3 * (size_t)owner[t]], &hi[3 * (size_t)owner[t]]));
+  const std::vector<uint32_t> sorted = SortByKey(keys, tris, tris_out, order_out);
+  // the hierarchy per segment, a block of nodes per record
   size_t base = 0;
-  std::vector<Split> split;
-  std::vector<uint32_t> rank;
   for (uint32_t r = 0; r < n_bvhs; ++r) {
-    const uint32_t s = seg.first[r], c = seg.count[r];
+    if (seg.count[r] == 0) return Fail(err, kEmptyRecord);  // (unreachable after OwnersFromNodes: every root reaches a leaf)
     bvhs_out[r] = bvhs[r];
     bvhs_out[r].first_index = (uint32_t)base;
-    auto put = [&](size_t at, const Slot& slot) {
-      nodes_out[at] = srt_bvh_node{};
-      nodes_out[at].first_child_or_prim_index = slot.count ? slot.index : (uint32_t)(base + 2 * (size_t)rank[slot.index - s] + 1);
-      nodes_out[at].prim_count = slot.count;
-    };
-    if (c == 0) return Fail(err, kEmptyRecord);  // (unreachable after OwnersFromNodes: every root reaches a leaf)
-    const Slot root = SegmentRoot(s, c, max_leaf);
-    uint32_t m = 0;
-    if (root.count == 0) {
-      split.resize(c - 1);
-      rank.resize(c - 1);
-      for (uint32_t k = 0; k + 1 < c; ++k) {
-        split[k] = SegmentSplit(sorted.data(), s, c, s + k);
-        rank[k] = m;
-        if (Survives(split[k], max_leaf)) ++m;
-      }
-    }
-    put(base, root);
-    for (uint32_t k = 0; root.count == 0 && k + 1 < c; ++k) {
-      if (!Survives(split[k], max_leaf)) continue;
-      put(base + 2 * (size_t)rank[k] + 1, LeftSlot(split[k], max_leaf));
-      put(base + 2 * (size_t)rank[k] + 2, RightSlot(split[k], max_leaf));
-    }
-    base += 2 * (size_t)m + 1;
+    base += PutSegment(sorted.data(), seg.first[r], seg.count[r], max_leaf, base, nodes_out);
   }
   *n_nodes_out = (uint32_t)base;
   return refit::RefitNodes(bvhs_out, n_bvhs, nodes_out, (uint32_t)base, tris_out, n_tris, verts, n_verts, err);
@@ -363,10 +339,6 @@ int CheckEnableModels(bool have_object, bool refit, uint32_t first_index, uint32
 
 bool ModelsSummaryValid(uint32_t m, uint32_t largest, uint32_t karras_pairs, uint32_t max_leaf) {
   return m <= karras_pairs && (m >= 1) == (karras_pairs >= 1) && largest <= max_leaf && (m == 0 || largest >= 1);
-}
-
-bool LeafSummaryValid(uint32_t m, uint32_t largest, uint32_t n_tris, uint32_t max_leaf) {
-  return m >= 1 && m <= n_tris - 1 && largest >= 1 && largest <= max_leaf;
 }
 
 bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out) {

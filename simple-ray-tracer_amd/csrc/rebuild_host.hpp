@@ -82,13 +82,10 @@ int BuildLBVHModels(const srt_bvh_record* bvhs, uint32_t n_bvhs, const srt_bvh_n
 // srt_query_enable_rebuild_models' contract before any device is touched (the owners come after it).
 int CheckEnableModels(bool have_object, bool refit, uint32_t first_index, uint32_t n_tris, std::string* err);
 
-// A collapsed rebuild's readback for several records: m may be 0 (every record a leaf root) and is at most the pairs
-// Karras' hierarchies hold; no leaf above max_leaf.
+// What a collapsed rebuild reads back beside the counts, checked before anything is planned from it: m is 0 exactly when
+// Karras' hierarchies hold no pair (every record a leaf root) and at most the pairs they hold, and with a pair the largest
+// leaf is in [1, max_leaf].  One record of n > max_leaf triangles: karras_pairs == n - 1, so 1 <= m <= n - 1.
 bool ModelsSummaryValid(uint32_t m, uint32_t largest, uint32_t karras_pairs, uint32_t max_leaf);
-
-// What a collapsed rebuild reads back beside the counts, checked before anything is planned from it: 1 <= m <= n - 1
-// pairs and a largest leaf in [1, max_leaf] (n > max_leaf >= 1).
-bool LeafSummaryValid(uint32_t m, uint32_t largest, uint32_t n_tris, uint32_t max_leaf);
 
 }  // namespace rebuild
 }  // namespace srt

@@ -226,8 +226,10 @@ static void TestArguments() {
   CHECK(CheckSetLeaf(true, true, 256, &err) == SRT_ERR_INVALID);
   CHECK(CheckSetLeaf(true, true, 1, &err) == SRT_OK && CheckSetLeaf(true, true, 255, &err) == SRT_OK);
 
-  CHECK(LeafSummaryValid(1, 2, 3, 2) && LeafSummaryValid(2, 1, 3, 2));
-  CHECK(!LeafSummaryValid(0, 2, 3, 2) && !LeafSummaryValid(3, 2, 3, 2) && !LeafSummaryValid(1, 0, 3, 2) && !LeafSummaryValid(1, 3, 3, 2));
+  // one record of 3 triangles above max_leaf 2: Karras' hierarchy holds 3 - 1 pairs
+  CHECK(ModelsSummaryValid(1, 2, 3 - 1, 2) && ModelsSummaryValid(2, 1, 3 - 1, 2));
+  CHECK(!ModelsSummaryValid(0, 2, 3 - 1, 2) && !ModelsSummaryValid(3, 2, 3 - 1, 2) && !ModelsSummaryValid(1, 0, 3 - 1, 2) &&
+        !ModelsSummaryValid(1, 3, 3 - 1, 2));
 }
 
 // The schedule takes the pair count it is given: m pairs of a collapsed tree, and none at all.

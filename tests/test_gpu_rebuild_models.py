@@ -177,15 +177,20 @@ def test_rebuild_then_refit_keeps_the_topology(torch, cases, name):
     check_hits(want, order, hits, O.Oracle(want).trace_closest(len(want.bvhs), rays))
 
 
-@pytest.mark.parametrize("name", MULTI)
-def test_no_state_is_carried_between_max_leaf_values(torch, cases, name):
+BOTH_WAYS = ((4, 1), (1, 4))
+
+
+@pytest.mark.parametrize("name,changes", [pytest.param(name, BOTH_WAYS, id=name) for name in MULTI] + [
+    # m > 0 pairs (the record of 64), then every record a leaf root: m == 0 and pair 0 zeroed
+    pytest.param("three", ((4, 255),), id="three-4-then-255")])
+def test_no_state_is_carried_between_max_leaf_values(torch, cases, name, changes):
     """max_leaf 4 then 1 gives the dwords of a fresh max_leaf 1 object, and 1 then 4 those of a fresh max_leaf 4 one."""
     from srt_amd.query import Query
 
     keys = ("stack.entries", "stack.in_hbm", "stack.packed", "refit.heights", "refit.launches", "refit.bytes", "rebuild.depth",
             "rebuild.launches", "rebuild.pairs", "rebuild.max_leaf", "rebuild.leaf", "layout.pairs", "layout.roots",
             "layout.tris", "scene.bytes", "rebuild.records")
-    for first, second in ((4, 1), (1, 4)):
+    for first, second in changes:
         scene, verts, built, order, rays, oracle = cases(name, second)
         with Query(scene, refit=True, rebuild_models=True, rebuild_leaf=first) as q, \
                 Query(scene, refit=True, rebuild_models=True, rebuild_leaf=second) as once:
