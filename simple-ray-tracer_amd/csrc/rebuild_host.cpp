@@ -343,15 +343,12 @@ bool ModelsSummaryValid(uint32_t m, uint32_t largest, uint32_t karras_pairs, uin
 
 bool ScheduleFromCounts(const uint32_t* counts, int n_counts, uint32_t n_pairs, refit::Schedule* out) {
   refit::Schedule s;
-  while (s.heights < (uint32_t)n_counts && counts[s.heights] > 0) ++s.heights;
+  uint32_t heights = 0;
+  while (heights < (uint32_t)n_counts && counts[heights] > 0) ++heights;
   uint64_t total = 0;
   for (int h = 0; h < n_counts; ++h) total += counts[h];
-  s.first.assign((size_t)s.heights + 1, 0);
-  for (uint32_t h = 0; h < s.heights; ++h) s.first[h + 1] = s.first[h] + counts[h];
-  if (total != n_pairs || s.first[s.heights] != n_pairs) return false;  // a gap, or pairs that never arrived
-  s.tail_begin = s.heights;
-  while (s.tail_begin > 0 && s.first[s.tail_begin] - s.first[s.tail_begin - 1] <= refit::kBlock) --s.tail_begin;
-  s.launches = 1 + s.tail_begin + 1;
+  refit::CloseLevels(counts, heights, true, &s);
+  if (total != n_pairs || s.first[heights] != n_pairs) return false;  // a gap, or pairs that never arrived
   *out = std::move(s);
   return true;
 }

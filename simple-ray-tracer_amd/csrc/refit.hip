@@ -1,5 +1,5 @@
 // refit.hip -- the BVH refit of include/srt_refit.h: the host refit's C entry point, the refit data of a query
-// object created with SRT_QUERY_REFIT, the launches of refit.hpp's kernels, and the layout readback.  A
+// object created with SRT_QUERY_REFIT, the launches of refit_kernels.hpp's kernels, and the layout readback.  A
 // translation unit of its own beside query.hip, which creates the object (query_object.hpp).
 #include <hip/hip_runtime.h>
 
@@ -40,7 +40,6 @@ int Attach(srt_query* q, const query::Layout& lay, const srt_triangle* tris, uin
 
 int Enqueue(srt_query* q, const srt_vertex* verts_dev) {
   STAGE_HIP_OK(hipSetDevice(q->device));
-  const Schedule& s = q->schedule;
   RParams rp;
   std::memset(&rp, 0, sizeof rp);
   rp.pairs = q->d_pairs;
@@ -53,17 +52,7 @@ int Enqueue(srt_query* q, const srt_vertex* verts_dev) {
   rp.n_verts = q->n_verts;
   rp.n_tris = q->n_tris;
   rp.n_roots = q->n_bvhs + 1;
-  rp.tail_levels = s.heights - s.tail_begin;
-  hipLaunchKernelGGL(refit_tris_kernel, dim3((q->n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp);
-  STAGE_HIP_OK(hipGetLastError());
-  for (uint32_t h = 0; h < s.tail_begin; ++h) {
-    const uint32_t first = s.first[h], count = s.first[h + 1] - first;
-    hipLaunchKernelGGL(refit_level_kernel, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, q->stream, rp, first, count);
-    STAGE_HIP_OK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(refit_tail_kernel, dim3(1), dim3(kBlock), 0, q->stream, rp);
-  STAGE_HIP_OK(hipGetLastError());
-  return SRT_OK;
+  return Enqueue<PairLayout>(q->stream, rp, q->schedule);
 }
 
 }  // namespace refit

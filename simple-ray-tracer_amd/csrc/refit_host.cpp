@@ -115,7 +115,7 @@ Schedule BuildSchedule(const query::Layout& l) {
     *q = AsUint(l.pairs[4 * (size_t)p + 2 * slot].w);
     return true;
   };
-  constexpr uint32_t kUnknown = 0xFFFFFFFFu;
+  constexpr uint32_t kUnknown = kNoHeight;
   std::vector<uint32_t> height(n, kUnknown);
   std::vector<uint32_t> st;
   for (uint32_t p0 = 0; p0 < n; ++p0) {
@@ -141,16 +141,7 @@ Schedule BuildSchedule(const query::Layout& l) {
       }
     }
   }
-  for (uint32_t p = 0; p < n; ++p) s.heights = std::max(s.heights, height[p] + 1);
-  s.first.assign((size_t)s.heights + 1, 0);
-  for (uint32_t p = 0; p < n; ++p) ++s.first[(size_t)height[p] + 1];
-  for (uint32_t h = 0; h < s.heights; ++h) s.first[h + 1] += s.first[h];
-  s.order.resize(n);
-  std::vector<uint32_t> at(s.first.begin(), s.first.end() - 1);
-  for (uint32_t p = 0; p < n; ++p) s.order[at[height[p]]++] = p;  // ascending pair index inside a level
-  s.tail_begin = s.heights;
-  while (s.tail_begin > 0 && s.first[s.tail_begin] - s.first[s.tail_begin - 1] <= kBlock) --s.tail_begin;
-  s.launches = 1 + s.tail_begin + 1;
+  SortByHeight(height, true, [](uint32_t p) { return p; }, &s, &s.order);  // (every pair has a height by now)
   return s;
 }
 

@@ -10,11 +10,10 @@
 
 #include "../../include/srt_amd.h"
 #include "query_host.hpp"
+#include "refit_levels.hpp"
 
 namespace srt {
 namespace refit {
-
-constexpr uint32_t kBlock = 256;  // lanes per block of the refit kernels; a level of at most this many pairs fuses
 
 // The fold of include/srt_refit.h, one component.
 inline float FoldMin(float m, float v) { return v < m ? v : m; }
@@ -30,15 +29,10 @@ int RefitNodes(const srt_bvh_record* bvhs, uint32_t n_bvhs, srt_bvh_node* nodes,
                const srt_triangle* tris, uint32_t n_tris, const srt_vertex* verts, uint32_t n_verts, std::string* err);
 
 // The device refit walks the pairs bottom-up by height: 0 when both slots of a pair are leaves, else 1 + the
-// largest height of its internal slots' pairs.  `order` lists the pair indices by height; level h is
-// order[first[h] .. first[h+1]).  Levels below `tail_begin` get a launch each; the maximal suffix of levels
-// that each hold at most kBlock pairs runs in one block, which then computes the roots.
-struct Schedule {
+// largest height of its internal slots' pairs.  `order` lists the pair indices by height (refit_levels.hpp); the
+// tail's block then computes the roots, and `launches` always counts the triangle kernel.
+struct Schedule : Levels {
   std::vector<uint32_t> order;  // n_pairs entries
-  std::vector<uint32_t> first;  // heights + 1 entries
-  uint32_t heights = 0;
-  uint32_t tail_begin = 0;      // first level of the one-block tail (== heights when no level fuses)
-  uint32_t launches = 0;        // the triangle kernel + one per level below tail_begin + the tail
 };
 Schedule BuildSchedule(const query::Layout& l);
 

@@ -1,5 +1,5 @@
 // scene_refit.hip -- the path tracer's scene refit (include/srt_scene_refit.h): the object an upload hands out,
-// the launches of scene_refit.hpp's kernels on the context's stream, and the readback of a context's device
+// the launches of refit_kernels.hpp's kernels on the context's stream, and the readback of a context's device
 // scene.  A translation unit of its own beside pathtrace.hip, which it only reads: the context's fields through
 // context.hpp, the device constants through traversal.hpp.  pathtrace.hip and its headers (the device code
 // srt_code_hash identifies) are unchanged.
@@ -208,7 +208,6 @@ int srt_scene_refit_destroy(struct srt_scene_refit* r) {
 }
 
 int srt_scene_refit(struct srt_scene_refit* r, const srt_vertex* verts_dev, uint32_t n_verts, uint32_t flags) {
-  using srt::scene_refit::kBlock;
   if (!r) return SRT_ERR_INVALID;
   if (!verts_dev || !srt::stage::Aligned(verts_dev, 16)) {
     srt::SetError("srt_scene_refit: verts_dev must be a 16-byte aligned device pointer");
@@ -231,7 +230,6 @@ int srt_scene_refit(struct srt_scene_refit* r, const srt_vertex* verts_dev, uint
   }
   HIP_OK(hipSetDevice(c->device));
   if (int rq = srt::Quiesce(c)) return rq;  // pipelined launches still read the old boxes
-  const srt::scene_refit::Schedule& s = r->schedule;
   srt::scene_refit::SParams sp;
   std::memset(&sp, 0, sizeof sp);
   sp.nodes = c->d_nodes;
@@ -244,19 +242,7 @@ int srt_scene_refit(struct srt_scene_refit* r, const srt_vertex* verts_dev, uint
   sp.n_verts = n_verts;
   sp.n_tris = r->n_tris;
   sp.ref_or = c->ref_or;
-  sp.tail_levels = s.heights - s.tail_begin;
-  if (r->n_tris > 0) {
-    hipLaunchKernelGGL(srt::scene_refit::tris_kernel, dim3((r->n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, sp);
-    HIP_OK(hipGetLastError());
-  }
-  for (uint32_t h = 0; h < s.tail_begin; ++h) {
-    const uint32_t first = s.first[h], count = s.first[h + 1] - first;
-    hipLaunchKernelGGL(srt::scene_refit::level_kernel, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, sp,
-                       first, count);
-    HIP_OK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(srt::scene_refit::tail_kernel, dim3(1), dim3(kBlock), 0, c->stream, sp);
-  HIP_OK(hipGetLastError());
+  if (int rc = srt::refit::Enqueue<srt::scene_refit::SlotLayout>(c->stream, sp, r->schedule)) return rc;
   // every stream the context launches on waits for the refit (a slot's launch otherwise waits only for that
   // slot's last accumulation)
   HIP_OK(hipEventRecord(r->done, c->stream));

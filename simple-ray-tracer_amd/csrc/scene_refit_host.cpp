@@ -9,7 +9,7 @@ namespace scene_refit {
 bool BuildSchedule(const uint32_t* ref, const uint32_t* cnt, uint32_t n_slots, uint32_t ref_or, const uint32_t* roots,
                    uint32_t n_roots, const uint32_t* tri_of_slot, uint32_t n_tri_slots, uint32_t n_tris, Schedule* out) {
   Schedule s;
-  constexpr uint32_t kUnknown = 0xFFFFFFFFu, kOpen = 0xFFFFFFFEu;
+  constexpr uint32_t kUnknown = refit::kNoHeight, kOpen = 0xFFFFFFFEu;
   std::vector<uint32_t> height(n_slots, kUnknown);
   std::vector<uint32_t> st;
   for (uint32_t r = 0; r < n_roots; ++r) {
@@ -39,22 +39,8 @@ bool BuildSchedule(const uint32_t* ref, const uint32_t* cnt, uint32_t n_slots, u
       }
     }
   }
-  for (uint32_t i = 0; i < n_slots; ++i)
-    if (height[i] != kUnknown) s.heights = std::max(s.heights, height[i] + 1);
-  s.first.assign((size_t)s.heights + 1, 0);
-  for (uint32_t i = 0; i < n_slots; ++i)
-    if (height[i] != kUnknown) ++s.first[(size_t)height[i] + 1];
-  for (uint32_t h = 0; h < s.heights; ++h) s.first[h + 1] += s.first[h];
-  s.order.resize(s.first[s.heights]);
-  std::vector<uint32_t> at(s.first.begin(), s.first.end() - 1);
-  for (uint32_t i = 0; i < n_slots; ++i) {
-    if (height[i] == kUnknown) continue;
-    const uint32_t t = cnt[i] > 0 ? (tri_of_slot ? tri_of_slot[ref[i]] : ref[i]) : 0u;
-    s.order[at[height[i]]++] = Entry{i, t};
-  }
-  s.tail_begin = s.heights;
-  while (s.tail_begin > 0 && s.first[s.tail_begin] - s.first[s.tail_begin - 1] <= kBlock) --s.tail_begin;
-  s.launches = (n_tris > 0 ? 1u : 0u) + s.tail_begin + 1;
+  auto entry = [&](uint32_t i) { return Entry{i, cnt[i] > 0 ? (tri_of_slot ? tri_of_slot[ref[i]] : ref[i]) : 0u}; };
+  refit::SortByHeight(height, n_tris > 0, entry, &s, &s.order);  // (the slots no root reaches stay kUnknown)
   *out = std::move(s);
   return true;
 }

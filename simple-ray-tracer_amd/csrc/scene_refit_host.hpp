@@ -8,11 +8,12 @@
 #include <vector>
 
 #include "../../include/srt_amd.h"
+#include "refit_levels.hpp"
 
 namespace srt {
 namespace scene_refit {
 
-constexpr uint32_t kBlock = 256;  // lanes per block of the kernels; a height of at most this many nodes fuses
+using refit::kBlock;
 
 // One node to refit: its slot of the device node array and, for a leaf, the leaf's first input triangle (the
 // fold walks the input order; the record itself holds the triangle's slot).
@@ -21,16 +22,10 @@ struct Entry {
 };
 
 // The nodes go bottom-up by height: 0 for a leaf, else 1 + the larger height of the two children.  `order`
-// lists the reached slots by height, ascending slot inside one; height h is order[first[h] .. first[h+1]).
-// Heights below `tail_begin` get a launch each; the maximal suffix of heights that each hold at most kBlock
-// nodes runs in one block.
-struct Schedule {
+// lists the reached slots by height, ascending slot inside one (refit_levels.hpp); `launches` counts the triangle
+// kernel only when there are triangles.
+struct Schedule : refit::Levels {
   std::vector<Entry> order;
-  std::vector<uint32_t> first;  // heights + 1 entries
-  uint32_t heights = 0;
-  uint32_t tail_begin = 0;      // first height of the one-block tail (== heights when none fuses)
-  uint32_t launches = 0;        // the triangle kernel (when there are triangles) + one per height below
-                                // tail_begin + the tail
 };
 
 // `ref` / `cnt`: the .w fields of the n_slots records of the device node array (scene_image.hpp: an internal

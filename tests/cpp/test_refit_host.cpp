@@ -102,6 +102,26 @@ static void TestSchedule() {
     s = BuildSchedule(Pairs(ps));
     CHECK(s.heights == 10 && s.first[1] == 512 && s.first[2] - s.first[1] == 556 && s.tail_begin == 2 && s.launches == 4);
   }
+  // the tail rule every schedule shares (refit_levels.hpp) at its boundary: a height of exactly kBlock entries
+  // fuses, one of kBlock + 1 gets a launch of its own, and with it every height under it
+  {
+    srt::refit::Levels l;
+    const uint32_t fuse[3] = {256, 256, 1}, wide[3] = {256, 257, 1};
+    static_assert(srt::refit::kBlock == 256, "the counts above are kBlock and kBlock + 1");
+    srt::refit::CloseLevels(fuse, 3, true, &l);
+    CHECK(l.heights == 3 && l.tail_begin == 0 && l.launches == 2 && l.first == std::vector<uint32_t>({0, 256, 512, 513}));
+    srt::refit::CloseLevels(wide, 3, true, &l);
+    CHECK(l.heights == 3 && l.tail_begin == 2 && l.launches == 4 && l.first == std::vector<uint32_t>({0, 256, 513, 514}));
+    srt::refit::CloseLevels(wide, 3, false, &l);  // a caller without triangles counts no triangle kernel
+    CHECK(l.tail_begin == 2 && l.launches == 3);
+    srt::refit::CloseLevels(wide, 0, true, &l);
+    CHECK(l.heights == 0 && l.tail_begin == 0 && l.launches == 2 && l.first == std::vector<uint32_t>({0}));
+    // the counting sort: ascending index inside a height, the indices without a height left out
+    std::vector<uint32_t> order;
+    srt::refit::SortByHeight<uint32_t>({1, 0, srt::refit::kNoHeight, 0, 2, 1}, true, [](uint32_t i) { return 10 + i; }, &l, &order);
+    CHECK(order == std::vector<uint32_t>({11, 13, 10, 15, 14}) && l.first == std::vector<uint32_t>({0, 2, 4, 5}));
+    CHECK(l.heights == 3 && l.tail_begin == 0 && l.launches == 2);
+  }
 }
 
 static srt_vertex V(float x, float y, float z) {
