@@ -13,6 +13,13 @@ alone.  Two more for the structure alone, EXTRA: "ones": three models of one tri
 the pair array's n - 1 slots all unused); "nested": (a) with the grid where refit_ref.grid_triangles(2) puts it, in the
 cube's bottom face -- one record's box overlapping another's, where a box or a key taken over the wrong triangles shows (no ray from
 outside reaches the grid first there, which is why (a) moves it).  Every scene is rebuilt at refit_ref.wave(verts, 0.25, 0.3), the amplitude of the one-model tests.
+
+Many records, MANY and MANY_MIXED: "many<R>" for R of MANY_R, R small models of 1, 2, 3, 5 and 9 triangles on a jittered
+lattice, each with a material of its own, among them a triangle without extent in z, 64 coincident triangles and pairs of
+records that coincide (many_triangles); "many_big": many300 with record 150 a grid of 882 triangles, so that in creation
+order some 256-triangle blocks of seg_box_kernel lie inside one record and two straddle its ends; and "many300_shuffled",
+"many_big_shuffled": those two through `shuffled`, the leaves' runs permuted in the triangle array, so that consecutive
+triangles belong to different records.
 """
 import dataclasses
 
@@ -28,9 +35,131 @@ EXTRA = ("ones", "nested")
 GRID_SHIFT = 14.0  # Rubik spans about +-9 around the origin: the grid lies outside it
 LEAVES = (1, 4)
 
+# -- many records --------------------------------------------------------------------------------------------------------
+# many(R): R small models on a jittered lattice, one material each.  R steps over the record-bit counts of the sort's end
+# bit (4 | 5: 2 | 3 bits, 64 | 65: 6 | 7, 256 | 257: 8 | 9, the last past one 8-bit radix digit above bit 32) and over the
+# 256 lanes of the refit's roots loop (n_roots = R + 1: 257, 258, 301).
+MANY_R = (4, 5, 64, 65, 256, 257, 300)
+MANY = tuple(f"many{R}" for R in MANY_R)                     # the rule-level tests
+MANY_MIXED = ("many_big", "many300_shuffled", "many_big_shuffled")
+MANY_HEAVY = ("many5", "many257", "many300") + MANY_MIXED    # hits, stages, refit
+# scene_rays' per_record for these scenes.  A ray aimed into the box of a one-triangle model meets the triangle about one
+# time in seven, so 24 a record leave one record in a hundred unfound (the oracle alone shows it); 64 find every record
+# three times and more.  21 k rays at 300 records: a third of a second of the oracle per tree.
+MANY_RAYS = 64
+CYCLE = (1, 2, 3, 5, 9)
+SPACING, JITTER = 12.0, 2.0  # the models are pieces of grid_triangles(3), at most 3.9 across: boxes 4.1 apart at least,
+#   and sparse enough that rays from outside find the inner ones
+AXIS_RECORD, COPIES_RECORD = 1, 2
+BIG_RECORD, BIG_GRID = 150, 21  # grid_triangles(21): 882 triangles, at least 3 * 256 + 100 and under the restatement's 1 000
+SHUFFLE_SEED = 17
+
+
+def many_pairs(R):
+    """{later record: earlier record} of the records with identical geometry at identical positions: four pairs over the
+    cycle's counts 5, 9, 1 and 3 from R = 80 on, and below as many of them as stay under 5% of R (three at 64 and 65, none
+    at 4 and 5): no ray finds the later record of a pair first, and the rays must find all but 5% of the records."""
+    return dict(list({40: 3, 45: 4, 50: 5, 55: 7}.items())[:min(4, R // 20)])
+
+
+def many_triangles(R, big=False):
+    """Per record its xyz9 rows.  Record k: CYCLE[k % 5] triangles of refit_ref.grid_triangles(3) from row k % 7 on, at
+    lattice point k of a cube of ceil(cbrt(R)) points a side, jittered (seed 29); but record 1 one triangle in a plane
+    z = const (no extent in z), record 2 rebuild_ref.copies_triangles() -- 64 coincident triangles -- and the later record
+    of every pair of many_pairs the earlier one's rows.  `big`: record BIG_RECORD a bumped grid beside the lattice."""
+    base = RR.grid_triangles(3)
+    side = int(np.ceil(R ** (1.0 / 3.0) - 1e-9))
+    rng = np.random.default_rng(29)
+    jitter = rng.uniform(-JITTER, JITTER, size=(R, 3))
+    out = []
+    for k in range(R):
+        at = (SPACING * np.asarray((k % side, (k // side) % side, k // (side * side))) + jitter[k]).astype(np.float32)
+        if k == AXIS_RECORD:
+            tri = np.asarray([[0.25, 0.5, 1.0, 2.5, 0.75, 1.0, 1.0, 3.0, 1.0]], np.float32)
+        elif k == COPIES_RECORD:
+            tri = BR.copies_triangles()
+        else:
+            tri = base[k % 7:k % 7 + CYCLE[k % len(CYCLE)]]
+        out.append((tri.reshape(-1, 3, 3) + at).reshape(-1, 9))
+    if big:
+        tri = RR.grid_triangles(BIG_GRID).reshape(-1, 3, 3).copy()
+        x, y = tri[:, :, 0], tri[:, :, 1]  # lifted as rebuild_ref.bump lifts vertices
+        tri[:, :, 2] = (tri[:, :, 2] + np.float32(0.6) * np.sin(np.float32(0.7) * x + np.float32(0.3)) * np.cos(np.float32(0.5) * y))
+        out[BIG_RECORD] = (tri.astype(np.float32) - np.asarray((BIG_GRID + 5.0, 0.0, 0.0), np.float32)).reshape(-1, 9)
+    for later, earlier in many_pairs(R).items():
+        out[later] = out[earlier].copy()
+    return out
+
+
+def many_kd(k):
+    """Record k's diffuse colour: one of 8^3, so the material -- and the albedo a surface stage reads -- names the record."""
+    return ((k % 8 + 1) / 8.0, (k // 8 % 8 + 1) / 8.0, (k // 64 + 1) / 8.0)
+
+
+def many(R, big=False):
+    """(scene, verts): the R models in record order, every triangle's material its record; rebuilt at the wave of every
+    other scene, with record 1's three vertices put back into one plane z = const (the wave moves z by a sine of x and y)."""
+    scene = S.Scene.from_models([S.model_from_triangles(tri, kd=many_kd(k)) for k, tri in enumerate(many_triangles(R, big))])
+    verts = RR.wave(scene.verts, 0.25, 0.3)
+    flat = scene.tris["v"][owners(scene) == AXIS_RECORD].reshape(-1)
+    verts["pos"][flat, 2] = verts["pos"][flat[0], 2]
+    return scene, verts
+
+
+def leaf_runs(scene):
+    """The (first, count) runs of the leaves reachable from every record's root, in the order of the walk."""
+    runs = []
+    for b in scene.bvhs:
+        stack = [int(b["first_index"])]
+        while stack:
+            j = stack.pop()
+            first, count = int(scene.nodes[j]["first"]), int(scene.nodes[j]["count"])
+            if count:
+                runs.append((j, first, count))
+            else:
+                stack += [first + 1, first]
+    return runs
+
+
+def shuffled(scene, seed=SHUFFLE_SEED):
+    """`scene` with the runs of its leaves permuted in the triangle array (what "swapped" does for two blocks, per leaf):
+    tris and tri_input move, every leaf's `first` follows.  The same records own the same triangles, but consecutive
+    triangles of the array now belong to different records."""
+    runs = leaf_runs(scene)
+    nodes = scene.nodes.copy()
+    src, at = [], 0
+    for k in np.random.default_rng(seed).permutation(len(runs)):
+        j, first, count = runs[k]
+        nodes[j]["first"] = at
+        src.append(np.arange(first, first + count))
+        at += count
+    src = np.concatenate(src)
+    assert at == len(scene.tris) and (np.sort(src) == np.arange(at)).all()  # the leaves tile the array
+    return dataclasses.replace(scene, nodes=nodes, tris=scene.tris[src].copy(), tri_input=scene.tri_input[src].copy())
+
+
+def many_scene(name):
+    """The scene of a name of MANY or MANY_MIXED."""
+    core = name[:-len("_shuffled")] if name.endswith("_shuffled") else name
+    scene, verts = many(300, big=True) if core == "many_big" else many(int(core[len("many"):]))
+    return (shuffled(scene) if core != name else scene), verts
+
+
+def many_exempt(R):
+    """The records of many(R) no ray from outside finds first: the later record of every coincident pair (the earlier one
+    is visited first and keeps the hit).  The construction places no record inside another."""
+    return sorted(many_pairs(R))
+
+
+def rays_of(name, scene, verts):
+    """scene_rays, with MANY_RAYS a record on the many-record scenes."""
+    return scene_rays(scene, verts, per_record=MANY_RAYS) if name.startswith("many") else scene_rays(scene, verts)
+
 
 def make_scene(name, rubik_model):
     """(scene, verts): the scene a query object is created from and the vertices it is rebuilt at."""
+    if name.startswith("many"):
+        return many_scene(name)
     if name in ("two", "swapped", "nested"):
         shift = 0.0 if name == "nested" else GRID_SHIFT
         grid = RR.grid_triangles(2).reshape(-1, 3, 3) + np.asarray((shift, 0.0, 0.0), np.float32)

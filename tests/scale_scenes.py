@@ -19,6 +19,8 @@ The thresholds and where they come from:
 "soup1m": render.synthetic_model(1,052,672): onesweep.
 "knot70k_and_rubik": two records, knot70k and Rubik moved outside the knot's box along x; record 0 fills 272 whole
   blocks of seg_box_kernel, Rubik the blocks behind.
+"knot70k_and_rubik_shuffled": that scene through rebuild_models_ref.shuffled, the runs of its leaves permuted in the
+  triangle array: the two records' triangles interleaved across every block of seg_box_kernel and every tile of the sort.
 Every scene but the soup is rebuilt and refit at refit_ref.wave(verts, 0.25, 0.3), as the small tests' scenes are; the
 wave moves coincident vertices alike.  The soup is rebuilt where it was created: its midpoint tree gives way to the
 linear one all the same.
@@ -42,7 +44,7 @@ N_KNOT = 2 * 272 * 128    # 69,632
 N_BASES = 17
 N_SOUP = 1_052_672
 LEAVES = (1, 4)           # the max_leaf values tests/test_gpu_scale.py rebuilds at
-SCENES = ("knot70k", "clusters", "soup1m", "knot70k_and_rubik")
+SCENES = ("knot70k", "clusters", "soup1m", "knot70k_and_rubik", "knot70k_and_rubik_shuffled")
 
 
 def box_loop_threshold():
@@ -124,6 +126,8 @@ def make_scene(name, rubik_model=None):
     elif name == "soup1m":
         scene = S.Scene.from_models([R.synthetic_model(N_SOUP)])
         return scene, scene.verts  # (no wave: the sort is what this size is for, and the test stays short)
+    elif name == "knot70k_and_rubik_shuffled":
+        scene = MR.shuffled(knot_and_rubik(rubik_model))
     else:
         assert name == "knot70k_and_rubik"
         scene = knot_and_rubik(rubik_model)

@@ -6,7 +6,11 @@ against the CPU oracle on the mirror's arrays, the hit position mapped through t
 tests/test_rebuild_models_api.py holds the mirror to the single-model mirror and to a numpy restatement of the rule; the
 scenes are tests/rebuild_models_ref.py's: Rubik beside a small grid, three records (64 coincident triangles, one
 triangle, three triangles), the first scene with its triangle blocks exchanged, and Rubik alone; for the structure also
-three one-triangle models (no pair) and the grid unmoved, in the cube (the records' boxes overlap).
+three one-triangle models (no pair) and the grid unmoved, in the cube (the records' boxes overlap); and the many-record
+scenes -- 4 to 300 small models, one of them large in "many_big", in creation order and with the records' triangles
+interleaved -- for what depends on the number or the placement of the records: the sort's end bit, the roots loop of the
+refit's tail past 256, seg_box_kernel's one-owner and mixed-owner blocks, owners that are not contiguous, ties between
+coincident records, and the matrix of a high record.
 """
 import dataclasses
 
@@ -18,6 +22,7 @@ import rebuild_models_ref as MR
 import rebuild_ref as BR
 import refit_ref as RR
 import srt_amd as S
+import surface_refit_ref as SRR
 from conftest import OBJECTS, bits_equal
 from oracle import pyoracle as O
 from test_gpu_queries import MISS, to_dev
@@ -26,6 +31,12 @@ from test_gpu_rebuild import expected_schedule, verts_dev
 pytestmark = pytest.mark.gpu
 
 MULTI = ("two", "three", "swapped")
+MANY_ALL = MR.MANY + MR.MANY_MIXED
+
+
+def per_record(name):
+    """check_hits' floor of rays per record: the many-record scenes have 64 rays a record, and check_many_found instead."""
+    return 0 if name == "nested" or name.startswith("many") else 50
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +63,7 @@ class Cases:
         if (name, max_leaf) not in self.made:
             scene, verts = self.scenes[name]
             built, order = S.build_lbvh_models(scene, verts, max_leaf=max_leaf)
-            rays = MR.scene_rays(scene, verts)
+            rays = MR.rays_of(name, scene, verts)
             self.made[name, max_leaf] = (scene, verts, built, order, rays, O.Oracle(built).trace_closest(len(built.bvhs), rays))
         return self.made[name, max_leaf]
 
@@ -79,6 +90,16 @@ def check_hits(built, order, hits, oracle, per_record=50):
     for r in range(len(built.bvhs)):
         assert (hits["bvh"][hit] == r).sum() >= per_record, f"the rays must find record {r}"
     return hit
+
+
+def check_many_found(name, built, hits, hit):
+    """A many-record scene: the object is in the regime the scene is named for, and the hits name every record but the
+    later one of each coincident pair -- a record merged into its neighbour or lost would be missing here."""
+    R = len(built.bvhs)
+    assert R == (300 if "big" in name else int(name[4:].split("_")[0]))
+    found = set(hits["bvh"][hit].tolist())
+    assert sorted(set(range(R)) - found) == MR.many_exempt(R)
+    assert (hits["material"][hit] == hits["bvh"][hit]).all()  # every model has a material of its own
 
 
 def check_structure(q, built, order, max_leaf):
@@ -132,10 +153,17 @@ def check_counters(q, built, max_leaf, m):
 
 
 @pytest.mark.parametrize("max_leaf", MR.LEAVES)
-@pytest.mark.parametrize("name", MULTI + MR.EXTRA)
+@pytest.mark.parametrize("name", MULTI + MR.EXTRA + MANY_ALL)
 def test_structure_hits_and_counters_after_a_rebuild(torch, cases, name, max_leaf):
     """The rebuild, closest and occluded enqueued back to back on a non-default stream.  ("nested": no ray from outside
-    meets the grid in the cube first, so that scene counts no hits per record.)"""
+    meets the grid in the cube first, so that scene counts no hits per record.)
+
+    The many-record scenes are here for: the sort's end bit, 32 + 2 | 3, 6 | 7 and 8 | 9 record bits at 4 | 5, 64 | 65 and
+    256 | 257 records (one bit short merges two records' segments: the roots, the order and the hits' records differ); the
+    roots loop of the refit's tail past its 256 lanes (257 and 300 records: n_roots of 258 and 301, every root and the
+    ghost root compared); seg_box_kernel's blocks of one owner and the blocks straddling a record's ends ("many_big") and
+    its blocks of a hundred owners and more (the shuffled scenes); and interleaved owners -- pos_rec, seg, segment_of,
+    owner_of and the hit remap (the shuffled scenes: `triangle` is the creation index, `bvh` the record)."""
     from srt_amd.query import Query
 
     scene, verts, built, order, rays, oracle = cases(name, max_leaf)
@@ -154,14 +182,22 @@ def test_structure_hits_and_counters_after_a_rebuild(torch, cases, name, max_lea
         m = check_structure(q, built, order, max_leaf)
         check_counters(q, built, max_leaf, m)
         assert q.get_int("rebuild.count") == 1
-    hit = check_hits(built, order, hits, oracle, per_record=0 if name == "nested" else 50)
-    assert (occ == hit).all() and hit.sum() >= 100
+        if name.startswith("many"):
+            assert q.get_int("rebuild.records") == len(scene.bvhs) and q.get_int("layout.roots") == 32 * (len(scene.bvhs) + 1)
+    hit = check_hits(built, order, hits, oracle, per_record=per_record(name))
+    assert (occ == hit).all()
+    if name.startswith("many"):  # (few of the rays aimed at the whole lattice meet one of 4 or 5 small models)
+        check_many_found(name, built, hits, hit)
+    else:
+        assert hit.sum() >= 100
     if name == "ones":  # no pair at all: check_structure saw the n - 1 unused slots (max_leaf 1) or the one pair zero
         assert m == 0
 
 
-@pytest.mark.parametrize("name", MULTI)
+@pytest.mark.parametrize("name", MULTI + MR.MANY_HEAVY)
 def test_rebuild_then_refit_keeps_the_topology(torch, cases, name):
+    """(The many-record scenes: the refit over a device-built schedule of up to 300 trees, and its tail's roots loop past
+    256 lanes at 257 and 300 records; the shuffled ones with the triangle records permuted against the creation order.)"""
     from srt_amd.query import Query
 
     scene, verts, built, order, rays, _ = cases(name, 4)
@@ -174,17 +210,21 @@ def test_rebuild_then_refit_keeps_the_topology(torch, cases, name):
         m = check_structure(q, want, order, 4)
         check_counters(q, want, 4, m)
         assert q.get_int("rebuild.count") == 1 and q.get_int("refit.count") == 1
-    check_hits(want, order, hits, O.Oracle(want).trace_closest(len(want.bvhs), rays))
+    hit = check_hits(want, order, hits, O.Oracle(want).trace_closest(len(want.bvhs), rays), per_record=per_record(name))
+    if name.startswith("many"):
+        check_many_found(name, want, hits, hit)
 
 
 BOTH_WAYS = ((4, 1), (1, 4))
 
 
-@pytest.mark.parametrize("name,changes", [pytest.param(name, BOTH_WAYS, id=name) for name in MULTI] + [
+@pytest.mark.parametrize("name,changes", [pytest.param(name, BOTH_WAYS, id=name) for name in MULTI + ("many257", "many_big_shuffled")] + [
     # m > 0 pairs (the record of 64), then every record a leaf root: m == 0 and pair 0 zeroed
     pytest.param("three", ((4, 255),), id="three-4-then-255")])
 def test_no_state_is_carried_between_max_leaf_values(torch, cases, name, changes):
-    """max_leaf 4 then 1 gives the dwords of a fresh max_leaf 1 object, and 1 then 4 those of a fresh max_leaf 4 one."""
+    """max_leaf 4 then 1 gives the dwords of a fresh max_leaf 1 object, and 1 then 4 those of a fresh max_leaf 4 one.
+    ("many257": nine record bits in the sort and 258 roots; "many_big_shuffled": interleaved owners and mixed-owner blocks,
+    the record boxes accumulated by atomics into words the second rebuild has to find zeroed again.)"""
     from srt_amd.query import Query
 
     keys = ("stack.entries", "stack.in_hbm", "stack.packed", "refit.heights", "refit.launches", "refit.bytes", "rebuild.depth",
@@ -206,7 +246,7 @@ def test_no_state_is_carried_between_max_leaf_values(torch, cases, name, changes
             assert q.get_int("rebuild.count") == 2 and once.get_int("rebuild.count") == 1
             for key in keys:
                 assert q.get_int(key) == once.get_int(key), (key, first, second)
-            check_hits(built, order, q.closest(to_dev(torch, rays)).numpy(), oracle)
+            check_hits(built, order, q.closest(to_dev(torch, rays)).numpy(), oracle, per_record=per_record(name))
 
 
 @pytest.mark.parametrize("max_leaf", MR.LEAVES)
@@ -258,6 +298,106 @@ def test_a_moved_model_matrix_changes_the_hits_as_on_a_created_object(torch, cas
         assert (hits["triangle"][hit] == order[want["triangle"][hit]]).all() and (hits["triangle"][~hit] == MISS).all()
         for field in ("t", "normal", "material", "bvh"):
             assert hits[field].tobytes() == want[field].tobytes(), field
+
+
+@pytest.mark.parametrize("name", ("many300", "many_big_shuffled"))
+@pytest.mark.parametrize("max_leaf", MR.LEAVES)
+def test_a_tie_between_coincident_records_goes_to_the_first_visited(torch, cases, name, max_leaf):
+    """Ties across records: records 40, 45, 50 and 55 repeat records 3, 4, 5 and 7 triangle for triangle where they stand,
+    so every ray that meets one meets the other at the same t.  The closest hit keeps the first visited -- the roots are
+    visited in record order -- after a rebuild as inside one tree: `bvh` is the record the oracle reports on the mirror's
+    arrays, the earlier one, for at least one ray of every pair."""
+    from srt_amd.query import Query
+
+    scene, verts, built, order, rays, oracle = cases(name, max_leaf)
+    pairs = MR.many_pairs(len(scene.bvhs))
+    assert len(pairs) >= 4
+    tri_o = oracle[0]
+    hit = tri_o != MISS
+    record = np.where(hit, MR.bvh_of_position(built)[np.where(hit, tri_o, 0)], MISS)
+    with Query(scene, refit=True, rebuild_models=True, rebuild_leaf=max_leaf) as q:
+        q.rebuild(verts_dev(torch, verts))
+        assert q.get_int("rebuild.records") == len(scene.bvhs)
+        hits = q.closest(to_dev(torch, rays)).numpy()
+    own = MR.owners(scene)
+    for later, earlier in pairs.items():
+        tied = (record == earlier) | (record == later)
+        assert tied.sum() >= 1, f"no ray finds the pair ({earlier}, {later})"
+        assert (record[tied] == earlier).all()  # the oracle alone: the first visited
+        assert (hits["bvh"][tied] == earlier).all() and (hits["material"][tied] == earlier).all()
+        assert (own[hits["triangle"][tied]] == earlier).all()  # the creation index is one of the earlier record's
+        assert bits_equal(hits["t"][tied], oracle[1][tied]).all()
+
+
+def small_frame(r):
+    """A world -> model translation of its own for record r, a twentieth of a triangle's size: rays aimed at the record
+    still find it (record 255 is one triangle), at another t."""
+    frame = np.eye(4, dtype=np.float32)
+    frame[3, :3] = (0.05 + 0.0001 * r, -0.04, 0.03 + 0.001 * (r % 7))
+    return frame
+
+
+def test_matrices_of_high_records_after_a_rebuild(torch, cases):
+    """A high record's matrix: after a rebuild of 300 records, update_model_matrix on records 0, 255, 256 and 299 -- the
+    first, the last of the first 256 roots, the first past them and the last -- gives the hits of an object created from
+    the mirror's scene with the same matrices, and the oracle's."""
+    from srt_amd.query import Query
+
+    scene, verts, built, order, rays, oracle = cases("many300", 4)
+    moved_records = (0, 255, 256, 299)
+    moved = dataclasses.replace(built, bvhs=built.bvhs.copy())
+    for r in moved_records:
+        moved.bvhs[r]["frame"] = small_frame(r).reshape(16)
+    dev = to_dev(torch, rays)
+    tri_m = O.Oracle(moved).trace_closest(300, rays)[0]  # the oracle alone: the rays find the four where they moved to
+    found = MR.bvh_of_position(moved)[tri_m[tri_m != MISS]]
+    assert all((found == r).sum() >= 1 for r in moved_records)
+    with Query(scene, refit=True, rebuild_models=True, rebuild_leaf=4) as q, Query(moved) as created:
+        q.rebuild(verts_dev(torch, verts))
+        assert q.get_int("rebuild.records") == 300 > max(moved_records) >= 256
+        before = q.closest(dev).numpy()
+        for r in moved_records:
+            q.update_model_matrix(r, small_frame(r))
+        hits = q.closest(dev).numpy()
+        want = created.closest(dev).numpy()  # positions of the mirror's arrays, not creation indices
+    hit = check_hits(moved, order, hits, O.Oracle(moved).trace_closest(300, rays), per_record=0)
+    for r in moved_records:
+        mine = hit & (hits["bvh"] == r)
+        assert mine.sum() >= 1, f"no ray finds record {r} where it moved to"
+        assert (hits["t"][mine].view(np.uint32) != before["t"][mine].view(np.uint32)).any()
+    others = hit & ~np.isin(hits["bvh"], moved_records) & (before["bvh"] == hits["bvh"]) & (before["triangle"] == hits["triangle"])
+    assert others.sum() >= 1000 and (hits["t"][others].view(np.uint32) == before["t"][others].view(np.uint32)).all()
+    assert (hits["triangle"][hit] == order[want["triangle"][hit]]).all() and (want["triangle"][~hit] == MISS).all()
+    for field in ("t", "normal", "material", "bvh"):
+        assert hits[field].tobytes() == want[field].tobytes(), field
+
+
+def test_a_surface_object_shades_the_hits_of_300_rebuilt_records(torch, cases):
+    """The downstream stage on many records.  A Surface object created before the rebuild, refit to
+    the same vertices, shades the rebuilt object's hits as tests/surface_ref.py says on those vertices.  Every model has
+    a diffuse colour of its own, so a `bvh` or a `triangle` that is off by one record changes the albedo: the albedo of
+    every hit is its record's colour."""
+    from srt_amd.query import Query
+    from srt_amd.surface import ATTR_DTYPE, Surface
+
+    scene, verts, built, order, rays, oracle = cases("many300", 4)
+    dev = to_dev(torch, rays)
+    with Surface(scene, refit=True) as surf, Query(scene, refit=True, rebuild_models=True, rebuild_leaf=4) as q:
+        vd = verts_dev(torch, verts)
+        q.rebuild(vd)
+        surf.refit(vd)
+        assert q.get_int("rebuild.records") == 300
+        h = q.closest(dev)
+        out = surf.shade(dev, h)
+        surf.synchronize()
+        got, hits = out.cpu().numpy().view(ATTR_DTYPE).reshape(-1), h.numpy()
+    hit = check_hits(built, order, hits, oracle, per_record=0)
+    want = SRR.shade_refit(scene, verts, rays, hits, tex_albedo=scene.tex_albedo)
+    assert (got.view(np.uint32) == want.view(np.uint32)).all()
+    assert (got["hit"] == hit).all() and hit.sum() >= 1000
+    colour = np.asarray([MR.many_kd(r) for r in range(300)], np.float32)
+    assert (got["albedo"][hit] == colour[hits["bvh"][hit]]).all()
+    assert len(np.unique(got["albedo"][hit], axis=0)) == 300 - len(MR.many_exempt(300))
 
 
 def test_refusals_enqueue_nothing_and_leave_the_layout(torch, cases):

@@ -8,6 +8,7 @@ device arrays pairs / roots / tris as uint32 [n, 4]; the roots include the ghost
 import numpy as np
 import pytest
 
+import rebuild_models_ref as MR
 import refit_ref as RR
 import srt_amd as S
 from conftest import OBJECTS
@@ -68,6 +69,8 @@ def small_scene(name, rubik):
         return S.Scene.from_models([S.model_from_triangles(RR.grid_triangles(1))])
     if name == "five":
         return S.Scene.from_models([S.model_from_triangles(same_centroid_triangles())])
+    if name.startswith("many"):  # tests/rebuild_models_ref.py's many-record scenes, as the loader's builder made them
+        return MR.make_scene(name, rubik)[0]
     assert name == "two_models"
     return S.Scene.from_models([rubik, S.model_from_triangles(RR.grid_triangles(5))])
 
@@ -78,8 +81,10 @@ def assert_layouts_equal(got, want):
         assert (g == w).all(), f"{what}: {(g != w).sum()} dwords differ"
 
 
-@pytest.mark.parametrize("name", ["rubik", "grid", "one", "two", "five", "two_models"])
+@pytest.mark.parametrize("name", ["rubik", "grid", "one", "two", "five", "two_models", "many257", "many_big_shuffled"])
 def test_every_dword_equals_the_fresh_layout(torch, rubik, name):
+    """("many257", "many_big_shuffled": the roots loop of the tail's block past its 256 lanes -- 258 and 301 root records,
+    the ghost root the last -- and in the second the triangle records of interleaved owners.)"""
     from srt_amd.query import Query
 
     scene = small_scene(name, rubik)
@@ -88,7 +93,7 @@ def test_every_dword_equals_the_fresh_layout(torch, rubik, name):
         before = qd.layout()
         assert qd.get_int("refit") == 1 and qd.get_int("refit.count") == 0
         heights, launches = qd.get_int("refit.heights"), qd.get_int("refit.launches")
-        n_pairs = (len(scene.nodes) - 1) // 2
+        n_pairs = (len(scene.nodes) - len(scene.bvhs)) // 2  # (a tree of 2 m + 1 nodes a record)
         assert qd.get_int("refit.bytes") >= 16 * len(scene.tris) + 4 * n_pairs
         # the schedule, from the nodes alone: a launch for the triangles, one for each level under the maximal
         # suffix of levels of at most 256 pairs, and the one-block tail
@@ -112,12 +117,19 @@ def test_every_dword_equals_the_fresh_layout(torch, rubik, name):
             frame[3, :3] = (3.0, -2.0, 1.0)
             qd.update_model_matrix(1, frame)
             assert before[1].shape == (2 * 3, 4)  # two records and the ghost root
+        elif name.startswith("many"):
+            n_roots = qd.get_int("layout.roots") // 32  # two float4 a root record
+            assert n_roots == len(scene.bvhs) + 1 > 256 and before[1].shape == (2 * n_roots, 4)
+            assert (before[1][2 * 256:, :3] != 0).any()  # (boxes past the first 256 roots, which the refit must move)
         qd.refit(verts_dev(torch, verts))
         assert qd.get_int("refit.count") == 1
         got, want = qd.layout(), qf.layout()
         assert_layouts_equal(got, want)
         assert not (got[1] == before[1]).all() and not (got[2] == before[2]).all()  # and it is no no-op
         assert (got[2][-3:] == 0).all()  # the pad record
+        if name.startswith("many"):  # every root past the tail block's first trip moved too
+            moved = (got[1][0::2, :3] != before[1][0::2, :3]).any(1) | (got[1][1::2, :3] != before[1][1::2, :3]).any(1)
+            assert moved[256:].all() and moved.all()
 
 
 def test_hits_after_a_refit_match_the_oracle(torch, rubik_scene, rubik_case):
@@ -144,6 +156,29 @@ def test_hits_after_a_refit_match_the_oracle(torch, rubik_scene, rubik_case):
     tri_o, _ = check_closest(refit, 1, rays, hits)
     assert (tri_o == tri1).all()
     assert (occ == (tri_o != MISS)).all()
+
+
+def test_hits_after_a_refit_of_300_records(torch, rubik):
+    """The roots loop past 256: a refit of "many300" -- 301 root records, so the tail's block takes a second trip over its
+    256 lanes -- then closest and occluded; every field against the oracle on the host-refit scene, the records 256 to
+    299 among the hits."""
+    from srt_amd.query import Query
+
+    scene, verts = MR.make_scene("many300", rubik)
+    rays = MR.rays_of("many300", scene, verts)
+    own = MR.owners(scene)
+    with Query(scene, refit=True) as q:
+        n_roots = q.get_int("layout.roots") // 32
+        assert n_roots == 301 > 256
+        dev = to_dev(torch, rays)
+        q.refit(verts_dev(torch, verts))
+        hits = q.closest(dev).numpy()
+        occ = q.occluded(dev).cpu().numpy()
+    tri_o, _ = check_closest(S.refit_scene(scene, verts), 300, rays, hits, bvh_of=lambda tri: own[tri].astype(np.uint32))
+    hit = tri_o != MISS
+    assert (occ == hit).all()
+    found = set(hits["bvh"][hit].tolist())
+    assert sorted(set(range(300)) - found) == MR.many_exempt(300) and set(range(256, 300)) <= found
 
 
 def test_two_models_hits_after_a_refit(torch, rubik):

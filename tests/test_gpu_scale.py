@@ -9,6 +9,8 @@ own regime again, so a scene shrunk later fails instead of passing vacuously):
       move the stacks from LDS to HBM; the path tracer's own choice of global-scene mode, triangle slots and a top region;
   clusters  17 keys of 4,096 triangles each, every key in every block of the sort: the order among equal keys;
   knot70k_and_rubik  the 64-bit (record, key) sort on the merge path, seg_box_kernel's one-owner path 272 times;
+  knot70k_and_rubik_shuffled  the same two records interleaved leaf by leaf: mixed-owner blocks throughout, owners that
+      cross every tile of the sort, and the hit remap over an order that is no concatenation of two runs;
   soup1m (1,052,672 triangles)  onesweep.
 Python walks of the tree are used up to 70 k triangles, beside scale_scenes.pairs_from_nodes; at 1 M the vectorised
 forms alone.
@@ -309,6 +311,39 @@ def test_rebuild_of_two_records_at_scale(torch, cases, max_leaf):
         hits, occ = hits.numpy(), occ.cpu().numpy()
         m = MT.check_structure(q, built, order, max_leaf)
         MT.check_counters(q, built, max_leaf, m)  # rebuild.height.<h> among them
+        assert q.get_int("rebuild.count") == 1 and q.get_int("refit.launches") >= 2 + 3
+        assert q.get_int("stack.in_hbm") == SC.in_hbm(q.get_int("rebuild.depth")) == 1
+    hit = MT.check_hits(built, order, hits, oracle)
+    assert (occ == hit).all() and hit.sum() >= 100
+
+
+def test_rebuild_of_two_interleaved_records_at_scale(torch, cases):
+    """Interleaved owners past one sort tile: "knot70k_and_rubik" with the runs of its leaves permuted in the triangle array,
+    max_leaf 4, and the assertions of test_rebuild_of_two_records_at_scale.  Rubik's triangles lie in at least 100 of the
+    277 blocks, so seg_box_kernel takes its mixed-owner path there, the 64-bit sort gathers a record from every tile, and
+    pos_rec / seg / the hit remap work on owners that are nowhere contiguous in creation order."""
+    from srt_amd.query import Query
+
+    scene, verts, built, order, rays, oracle = cases("knot70k_and_rubik_shuffled", 4)
+    n = len(scene.tris)
+    own = MR.owners(scene)
+    assert len(scene.bvhs) == 2 and SC.box_loop_threshold() < n <= SC.MERGE_LIMIT
+    assert np.bincount(own).tolist() == [SC.N_KNOT, n - SC.N_KNOT]
+    assert sum(1 for i in range(0, n, 256) if len(set(own[i:i + 256].tolist())) == 2) >= 100  # mixed-owner blocks
+    assert (RR.pair_height_counts(built) > SC.LEVEL).sum() >= 3
+    stream = torch.cuda.Stream()
+    with Query(scene, stream=stream, refit=True, rebuild_models=True, rebuild_leaf=4) as q:
+        with torch.cuda.stream(stream):
+            v = verts_dev(torch, verts)
+            dev = to_dev(torch, rays)
+            q.rebuild(v)
+            hits = q.closest(dev)
+            occ = q.occluded(dev)
+        stream.synchronize()
+        hits, occ = hits.numpy(), occ.cpu().numpy()
+        m = MT.check_structure(q, built, order, 4)
+        MT.check_counters(q, built, 4, m)  # rebuild.height.<h> among them
+        assert q.get_int("rebuild.records") == 2
         assert q.get_int("rebuild.count") == 1 and q.get_int("refit.launches") >= 2 + 3
         assert q.get_int("stack.in_hbm") == SC.in_hbm(q.get_int("rebuild.depth")) == 1
     hit = MT.check_hits(built, order, hits, oracle)

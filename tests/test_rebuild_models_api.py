@@ -1,6 +1,6 @@
 """The device rebuild for scenes of several models (include/srt_rebuild_models.h), CPU only: the host mirror
 srt_bvh_build_lbvh_models against the single-model mirror run on every record alone and against a numpy restatement of the
-segmented rule (tests/rebuild_models_ref.py), with max_leaf 1 and 4; a one-record scene against srt_bvh_build_lbvh_leaf
+segmented rule (tests/rebuild_models_ref.py), with max_leaf 1 and 4, up to 300 records and with the records' triangles interleaved; a one-record scene against srt_bvh_build_lbvh_leaf
 byte for byte; the oracle on the mirror's arrays against the oracle on the host-refit scene; the refusals with their
 messages; the exported symbols; the C++ mirror; and the host pieces under ASan/UBSan as a stand-alone program."""
 import ctypes as C
@@ -21,6 +21,7 @@ from srt_amd import _lib
 
 MISS = 0xFFFFFFFF
 NAMES = ["srt_rebuild_models_abi_version", "srt_query_enable_rebuild_models", "srt_bvh_build_lbvh_models"]
+ALL = MR.SCENES + MR.EXTRA + MR.MANY + MR.MANY_MIXED
 
 
 def bits(a):
@@ -36,7 +37,7 @@ def rubik():
 def cases(rubik):
     """{name: (scene, verts, {max_leaf: (mirror-built scene, order)})}, once."""
     out = {}
-    for name in MR.SCENES + MR.EXTRA:
+    for name in ALL:
         scene, verts = MR.make_scene(name, rubik)
         out[name] = (scene, verts, {L: S.build_lbvh_models(scene, verts, max_leaf=L) for L in MR.LEAVES})
     return out
@@ -76,7 +77,7 @@ def test_scene_shapes(cases):
 
 
 @pytest.mark.parametrize("max_leaf", MR.LEAVES)
-@pytest.mark.parametrize("name", MR.SCENES + MR.EXTRA)
+@pytest.mark.parametrize("name", ALL)
 def test_mirror_is_the_single_model_mirror_per_record(cases, name, max_leaf):
     """Nodes, triangles and order equal srt_bvh_build_lbvh_leaf's on every record's triangles alone, concatenated in record
     order (internal references moved by the block's start, leaf references by the segment's)."""
@@ -115,7 +116,7 @@ def test_one_record_is_srt_bvh_build_lbvh_leaf_byte_for_byte(cases, max_leaf):
 
 
 @pytest.mark.parametrize("max_leaf", MR.LEAVES)
-@pytest.mark.parametrize("name", MR.SCENES + MR.EXTRA)
+@pytest.mark.parametrize("name", ALL)
 def test_mirror_agrees_with_the_numpy_rule(cases, name, max_leaf):
     scene, verts, built = cases[name]
     built, order = built[max_leaf]
@@ -158,6 +159,132 @@ def test_oracle_on_the_mirror_equals_the_oracle_on_the_refit_scene(cases, name):
             same |= hit & (own[np.where(hit, got, 0)] == 0) & (own[np.where(hit, tri_r, 0)] == 0)
             assert (hit & (own[np.where(hit, tri_r, 0)] > 0)).sum() >= 100  # the two small models are compared by triangle
         assert same.all(), f"{(~same).sum()} rays name another triangle"
+
+
+# -- many records, interleaved records ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", MR.MANY + ("many_big",))
+def test_many_scene_shapes(cases, name):
+    """What rebuild_models_ref.many promises, at the vertices the scenes are rebuilt at: the record count, the cycle of
+    triangle counts, the material naming the record, the coincident pairs, the record without extent in z (its key is 0
+    on that axis), the 64 equal keys, boxes that stay apart, and the record-bit count the name stands for."""
+    scene, verts, built = cases[name]
+    R = len(scene.bvhs)
+    own = MR.owners(scene)
+    assert R == (300 if name == "many_big" else int(name[4:])) and (own >= 0).all() and (np.diff(own) >= 0).all()
+    assert len(scene.mats) == R and (scene.tris["mat"] == own).all()
+    assert len(np.unique(scene.mats["diffuse"], axis=0)) == R
+    special = {MR.AXIS_RECORD: 1, MR.COPIES_RECORD: 64}
+    pairs = MR.many_pairs(R)
+    count = np.bincount(own)
+    p = MR.BR.positions(scene, verts)
+    k64 = MR.keys(scene, verts, own)
+    for r in range(R):
+        source = pairs.get(r, r)
+        want = 882 if (name == "many_big" and r == MR.BIG_RECORD) else special.get(source, MR.CYCLE[source % 5])
+        assert count[r] == want, r
+    assert set(MR.CYCLE) <= set(count[:min(R, 10)].tolist()) or R < 10
+    assert len(pairs) == (4 if R >= 80 else R // 20) and all(later > earlier for later, earlier in pairs.items())
+    for later, earlier in pairs.items():  # the same corner positions, triangle for triangle, up to the order in the array
+        a, b = p[own == later].reshape(-1, 9), p[own == earlier].reshape(-1, 9)
+        assert sorted(map(bytes, a)) == sorted(map(bytes, b))
+    flat = p[own == MR.AXIS_RECORD]
+    assert len(np.unique(flat[..., 2])) == 1 and len(np.unique(flat[..., 0])) > 1 and len(np.unique(flat[..., 1])) > 1
+    assert int(k64[own == MR.AXIS_RECORD][0]) & 0x09249249 == 0  # z's bits of the Morton code: ext > 0 is false there
+    assert len(np.unique(k64[own == MR.COPIES_RECORD])) == 1
+    lo = np.stack([p[own == r].min((0, 1)) for r in range(R)])
+    hi = np.stack([p[own == r].max((0, 1)) for r in range(R)])
+    apart = (lo[:, None] > hi[None]).any(2) | (hi[:, None] < lo[None]).any(2)
+    for later, earlier in pairs.items():
+        assert not apart[later, earlier]
+        apart[later, earlier] = apart[earlier, later] = True
+    assert (apart | np.eye(R, dtype=bool)).all()  # no record inside another, but the coincident ones
+    # the sort's end bit: 32 + the least b >= 1 with 2^b >= R
+    bits = max(1, int(R - 1).bit_length())
+    assert bits == {4: 2, 5: 3, 64: 6, 65: 7, 256: 8, 257: 9, 300: 9}[R]
+    assert int(k64.max() >> np.uint64(32)) == R - 1 and (int(k64.max()) >> (32 + bits)) == 0
+    if bits > 1:
+        assert int(k64.max()) >> (32 + bits - 1) == 1  # one bit less would merge records
+    # max_leaf 1 and 4 see leaf roots, records without a pair and real trees
+    for L in MR.LEAVES:
+        sizes = [len(nodes) for nodes in MR.blocks(built[L][0])]
+        assert 1 in sizes and max(sizes) >= 5 and (L > 1 or R < 8 or 3 in sizes)  # (records 6 and 7: two and three triangles)
+
+
+@pytest.mark.parametrize("name", ("two", "many300", "many_big"))
+def test_the_shuffle_interleaves_the_records_and_keeps_the_scene(cases, rubik, name):
+    """rebuild_models_ref.shuffled: every triangle is still owned exactly once and by the record that owned it, the owners
+    are no longer monotone along the array, and the tree over the moved triangles is the same tree (srt_bvh_refit gives
+    the creation boxes back)."""
+    scene = cases[name][0]
+    got = cases[name + "_shuffled"][0] if name != "two" else MR.shuffled(scene)
+    own, own_s = MR.owners(scene), MR.owners(got)  # (owners raises on a triangle met twice)
+    assert (own >= 0).all() and (own_s >= 0).all() and (np.diff(own) >= 0).all()
+    assert (np.diff(own_s) < 0).sum() >= len(scene.bvhs) // 2 and (np.diff(own_s) != 0).mean() > (0.25 if name != "two" else 0.001)  # (runs of one or two triangles)
+    assert sorted(got.tri_input.tolist()) == sorted(scene.tri_input.tolist()) and len(got.tris) == len(scene.tris)
+    back = np.argsort(got.tri_input, kind="stable")
+    there = np.argsort(scene.tri_input, kind="stable")
+    assert got.tris[back].tobytes() == scene.tris[there].tobytes()  # the same triangles under the same loader index
+    assert (own_s[back] == own[there]).all()
+    assert (got.nodes["count"] == scene.nodes["count"]).all()
+    inner = scene.nodes["count"] == 0
+    assert (got.nodes["first"][inner] == scene.nodes["first"][inner]).all()
+    refit = S.refit_scene(got, got.verts)
+    for f in ("min", "max"):
+        assert (refit.nodes[f] == scene.nodes[f]).all()
+    assert MR.shuffled(scene).tris.tobytes() == got.tris.tobytes()  # a fixed seed
+
+
+def owner_blocks(scene):
+    own = MR.owners(scene)
+    return [own[i:i + 256] for i in range(0, len(own), 256)]
+
+
+def test_blocks_of_one_owner_and_of_many(cases):
+    """seg_box_kernel's two paths, from owners() cut into its blocks of 256 triangles.  "many_big" in creation order: blocks
+    wholly inside record 150 (the one-owner fold, six atomics a block) and the two that straddle its ends.  Shuffled:
+    blocks of a hundred owners and more (six atomics a lane), and in "many_big_shuffled" blocks that record 150's runs
+    enter and leave in the middle, none of them one-owner."""
+    big = MR.BIG_RECORD
+    blocks = owner_blocks(cases["many_big"][0])
+    whole = [b for b in blocks if (b == big).all()]
+    straddle = [b for b in blocks if (b == big).any() and (b != big).any()]
+    assert len(whole) >= 2 and len(straddle) == 2
+    assert straddle[0][0] < big and straddle[0][-1] == big and straddle[1][0] == big and straddle[1][-1] > big
+    assert all(len(b) == 256 for b in whole)
+    mixed = [len(set(b.tolist())) for b in owner_blocks(cases["many300_shuffled"][0])]
+    assert len(mixed) >= 4 and min(mixed[:-1]) >= 100
+    blocks = owner_blocks(cases["many_big_shuffled"][0])
+    assert len(blocks) >= 8 and all(len(set(b.tolist())) > 1 for b in blocks)
+    inside = 0
+    for b in blocks:
+        m = b == big
+        enter, leave = np.flatnonzero(~m[:-1] & m[1:]), np.flatnonzero(m[:-1] & ~m[1:])
+        inside += len(enter) > 0 and len(leave) > 0 and enter[0] < leave[-1] and len(set(b.tolist())) >= 50
+    assert inside >= 4
+
+
+@pytest.mark.parametrize("name", MR.MANY_HEAVY)
+def test_rays_find_every_record_of_the_many(cases, name):
+    """The oracle alone, on the mirror-built scenes: every record is srt_hit.bvh of at least one ray -- but the later
+    record of each coincident pair, which no ray can find first; the exempt set is stated and at most 5% of R -- the
+    earlier record of every pair is found, and the two trees agree on t and on the record of every ray."""
+    scene, verts, built = cases[name]
+    R = len(scene.bvhs)
+    exempt = MR.many_exempt(R)
+    assert exempt == ([40, 45, 50, 55] if R >= 80 else []) and len(exempt) <= 0.05 * R
+    rays = MR.rays_of(name, scene, verts)
+    assert len(rays) == 2000 + MR.MANY_RAYS * R
+    found = {}
+    for L in MR.LEAVES:
+        b, order = built[L]
+        tri, t, _, st = O.Oracle(b).trace_closest(R, rays)
+        assert st["stack_overflow"] == 0
+        hit = tri != MISS
+        found[L] = (np.where(hit, MR.bvh_of_position(b)[np.where(hit, tri, 0)], MISS), t)
+        seen = set(found[L][0][hit].tolist())
+        assert sorted(set(range(R)) - seen) == exempt
+        assert all(earlier in seen for earlier in MR.many_pairs(R).values())
+    assert (found[1][0] == found[4][0]).all() and bits_equal(found[1][1], found[4][1]).all()
 
 
 def _mirror_args(scene, verts, max_leaf=1):

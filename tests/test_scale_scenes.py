@@ -161,6 +161,29 @@ def test_record_0_fills_whole_blocks_and_rubik_lies_outside(scenes):
         assert p[own == 1][..., 0].min() > p[own == 0][..., 0].max() + 1.0
 
 
+def test_the_shuffle_interleaves_the_two_records_in_every_block(scenes, rubik):
+    """"knot70k_and_rubik_shuffled": the same triangles under the same records, Rubik's spread over the whole array -- no
+    block of 256 has one owner for sure where Rubik's 1,188 triangles fall, and they fall into at least 100 of the 277
+    blocks -- and the mirror builds the same two trees as from the creation order, the order mapped through the shuffle."""
+    scene, verts = scenes["knot70k_and_rubik"]
+    got, verts_s = SC.make_scene("knot70k_and_rubik_shuffled", rubik)
+    assert verts_s.tobytes() == verts.tobytes()
+    own, own_s = MR.owners(scene), MR.owners(got)
+    assert np.bincount(own_s).tolist() == np.bincount(own).tolist() == [SC.N_KNOT, 1188]
+    mixed = sum(1 for i in range(0, len(own_s), 256) if len(set(own_s[i:i + 256].tolist())) == 2)
+    assert mixed >= 100
+    assert (got.tri_input[own_s == 1] >= SC.N_KNOT).all() and (got.tri_input[own_s == 0] < SC.N_KNOT).all()
+    a, oa = S.build_lbvh_models(scene, verts, max_leaf=4)
+    b, ob = S.build_lbvh_models(got, verts, max_leaf=4)
+    # equal keys (the knot has some) keep the array's order, which the shuffle changed: the trees' shapes and boxes agree,
+    # the triangles agree as sets per record
+    assert a.nodes["count"].tobytes() == b.nodes["count"].tobytes() and len(a.nodes) == len(b.nodes)
+    assert a.bvhs.tobytes() == b.bvhs.tobytes()
+    for f in ("min", "max"):
+        assert (a.nodes[f][0] == b.nodes[f][0]).all()
+    assert sorted(scene.tri_input[oa].tolist()) == sorted(got.tri_input[ob].tolist())
+
+
 def test_a_leaf_of_255():
     scene, verts = SC.leaf255_scene()
     tree, order = S.build_lbvh(scene, verts, max_leaf=255)
