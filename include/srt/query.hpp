@@ -1,6 +1,7 @@
 // srt/query.hpp -- header-only C++ mirror of include/srt_query.h, include/srt_refit.h, include/srt_rebuild.h,
-// include/srt_rebuild_leaf.h and include/srt_rebuild_models.h: srt::Query, RAII over the C ABI with the same method names,
-// AssetUtils::RefitBVH, AssetUtils::BuildLBVH and AssetUtils::BuildLBVHModels.
+// include/srt_rebuild_leaf.h, include/srt_rebuild_models.h and include/srt_query_sort.h: srt::Query, RAII over the C ABI
+// with the same method names, AssetUtils::RefitBVH, AssetUtils::BuildLBVH, AssetUtils::BuildLBVHModels and
+// AssetUtils::RayOrder.
 // Errors throw std::runtime_error carrying srt_last_error().
 #pragma once
 
@@ -10,6 +11,7 @@
 #include <utility>
 
 #include "../srt_query.h"
+#include "../srt_query_sort.h"
 #include "../srt_rebuild.h"
 #include "../srt_rebuild_leaf.h"
 #include "../srt_rebuild_models.h"
@@ -66,6 +68,17 @@ class Query {
   void occluded(const srt_ray* rays_dev, uint32_t n, uint8_t* occluded_dev) {
     Check(srt_query_occluded(q_, rays_dev, n, occluded_dev), "srt_query_occluded");
   }
+  // include/srt_query_sort.h: the same calls through a coherence-sorted order built on the device; the same results.
+  void ClosestSorted(const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
+    Check(srt_query_closest_sorted(q_, rays_dev, n, hits_dev), "srt_query_closest_sorted");
+  }
+  void OccludedSorted(const srt_ray* rays_dev, uint32_t n, uint8_t* occluded_dev) {
+    Check(srt_query_occluded_sorted(q_, rays_dev, n, occluded_dev), "srt_query_occluded_sorted");
+  }
+  // The last sorted call's permutation and sorted keys (host arrays of n; nullptr skips); synchronises.
+  void CopyRayOrder(uint32_t* order, uint32_t* keys, uint32_t n) {
+    Check(srt_query_copy_ray_order(q_, order, keys, n), "srt_query_copy_ray_order");
+  }
   int get_int(const char* name) const {
     int v = 0;
     Check(srt_query_get_int(q_, name, &v), name);
@@ -121,6 +134,13 @@ inline uint32_t BuildLBVHModels(const srt_bvh_record* bvhs, uint32_t n_bvhs, con
                                          nodes_out, &n_out, tris_out, order_out))
     throw std::runtime_error("srt_bvh_build_lbvh_models failed with status " + std::to_string(rc) + ": " + srt_last_error());
   return n_out;
+}
+
+// srt_ray_order: the host mirror of Query::ClosestSorted's ordering -- order[n], the stable sort of 0 .. n-1 by key;
+// keys[n] (sorted) and bounds[6] (lo xyz, hi xyz of the finite origins) may be nullptr.
+inline void RayOrder(const srt_ray* rays, uint32_t n, uint32_t* order, uint32_t* keys = nullptr, float* bounds = nullptr) {
+  if (int rc = srt_ray_order(rays, n, order, keys, bounds))
+    throw std::runtime_error("srt_ray_order failed with status " + std::to_string(rc) + ": " + srt_last_error());
 }
 
 }  // namespace AssetUtils

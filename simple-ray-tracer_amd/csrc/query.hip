@@ -14,6 +14,7 @@
 #include "query.hpp"
 #include "query_host.hpp"
 #include "query_object.hpp"
+#include "ray_order_host.hpp"
 #include "stage.hpp"
 
 using srt::stage::Aligned;
@@ -31,12 +32,17 @@ int LdsBlocksPerCu(size_t lds) {
   return lds == 0 ? 1 << 30 : (int)(128 / ((lds + gran - 1) / gran));
 }
 
-template <bool ANY>
+template <bool ANY, bool ORDER>
 const void* Instance(bool hbm, bool pack) {
-  if (hbm) return pack ? (const void*)srt::query::query_kernel<ANY, true, true>
-                       : (const void*)srt::query::query_kernel<ANY, true, false>;
-  return pack ? (const void*)srt::query::query_kernel<ANY, false, true>
-              : (const void*)srt::query::query_kernel<ANY, false, false>;
+  if (hbm) return pack ? (const void*)srt::query::query_kernel<ANY, true, true, ORDER>
+                       : (const void*)srt::query::query_kernel<ANY, true, false, ORDER>;
+  return pack ? (const void*)srt::query::query_kernel<ANY, false, true, ORDER>
+              : (const void*)srt::query::query_kernel<ANY, false, false, ORDER>;
+}
+
+const void* Instance(bool any, bool sorted, bool hbm, bool pack) {
+  if (any) return sorted ? Instance<true, true>(hbm, pack) : Instance<true, false>(hbm, pack);
+  return sorted ? Instance<false, true>(hbm, pack) : Instance<false, false>(hbm, pack);
 }
 
 int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bvhs) {
@@ -65,7 +71,7 @@ int Upload(srt_query* q, const srt::query::Layout& lay, const srt_bvh_record* bv
 }
 
 template <bool ANY>
-int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
+int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out, const uint32_t* order) {
   if (!q || (n && (!rays || !out))) return SRT_ERR_INVALID;
   if (n == 0) return SRT_OK;
   if (!Aligned(rays, 16) || (!ANY && !Aligned(out, 16))) {
@@ -77,7 +83,7 @@ int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
     return SRT_ERR_LIMIT;
   }
   STAGE_HIP_OK(hipSetDevice(q->device));
-  const int blocks = (int)std::min<uint64_t>((uint64_t)q->max_blocks[ANY ? 1 : 0], ((uint64_t)n + kBlock - 1) / kBlock);
+  const int blocks = (int)std::min<uint64_t>((uint64_t)(order ? q->max_blocks_sorted : q->max_blocks)[ANY ? 1 : 0], ((uint64_t)n + kBlock - 1) / kBlock);
   if (q->plan.in_hbm && blocks > q->stack_blocks) {  // grown when n grows (hipFree waits for the device)
     q->d_stack.Free();
     q->stack_blocks = 0;
@@ -103,9 +109,10 @@ int Launch(srt_query* q, const srt_ray* rays, uint32_t n, void* out) {
   qp.claim = 64u * (uint32_t)(q->claim_env > 0 ? q->claim_env : std::max<uint64_t>(1, std::min<uint64_t>(4, per)));
   qp.stack_entries = q->plan.entries;
   qp.refill_min = q->refill_min;
+  qp.order = order;
   STAGE_HIP_OK(hipMemsetAsync(q->d_ctr, 0, sizeof(uint32_t), q->stream));
   void* args[] = {&qp};
-  STAGE_HIP_OK(hipLaunchKernel(Instance<ANY>(q->plan.in_hbm, q->plan.packed), dim3((unsigned)blocks), dim3(kBlock), args,
+  STAGE_HIP_OK(hipLaunchKernel(Instance(ANY, order != nullptr, q->plan.in_hbm, q->plan.packed), dim3((unsigned)blocks), dim3(kBlock), args,
                           q->plan.lds_bytes, q->stream));
   q->last_blocks = blocks;
   return SRT_OK;
@@ -118,17 +125,22 @@ namespace query {
 
 // persistent grid: the blocks the device holds at once
 int PlanGrid(srt_query* q) {
-  for (int any = 0; any < 2; ++any) {
-    const void* fn = any ? Instance<true>(q->plan.in_hbm, q->plan.packed) : Instance<false>(q->plan.in_hbm, q->plan.packed);
+  for (int k = 0; k < 4; ++k) {
+    const int any = k & 1, sorted = k >> 1;
+    const void* fn = Instance(any != 0, sorted != 0, q->plan.in_hbm, q->plan.packed);
     if (q->plan.lds_bytes > 48 * 1024)
       STAGE_HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q->plan.lds_bytes));
     int per_cu = 0;
     STAGE_HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, q->plan.lds_bytes));
     per_cu = std::max(1, std::min(per_cu, LdsBlocksPerCu(q->plan.lds_bytes)));
     if (q->plan.in_hbm) per_cu = std::min(per_cu, 4);  // each block holds an HBM stack area
-    q->max_blocks[any] = per_cu * std::max(1, q->cu_count);
+    (sorted ? q->max_blocks_sorted : q->max_blocks)[any] = per_cu * std::max(1, q->cu_count);
   }
   return SRT_OK;
+}
+
+int EnqueueTrace(srt_query* q, bool any, const srt_ray* rays, uint32_t n, void* out, const uint32_t* order) {
+  return any ? Launch<true>(q, rays, n, out, order) : Launch<false>(q, rays, n, out, order);
 }
 
 }  // namespace query
@@ -223,14 +235,14 @@ int srt_query_update_model_matrix(srt_query* q, uint32_t index, const float fram
 }
 
 int srt_query_closest(srt_query* q, const srt_ray* rays_dev, uint32_t n, srt_hit* hits_dev) {
-  if (int rc = Launch<false>(q, rays_dev, n, hits_dev)) return rc;
+  if (int rc = Launch<false>(q, rays_dev, n, hits_dev, nullptr)) return rc;
   // a rebuilt object holds its triangle records in the LBVH's order (include/srt_rebuild.h)
   if (n && q->rebuild && q->rebuild->count > 0) return srt::rebuild::EnqueueRemap(q, hits_dev, n);
   return SRT_OK;
 }
 
 int srt_query_occluded(srt_query* q, const srt_ray* rays_dev, uint32_t n, uint8_t* occluded_dev) {
-  return Launch<true>(q, rays_dev, n, occluded_dev);
+  return Launch<true>(q, rays_dev, n, occluded_dev, nullptr);
 }
 
 int srt_query_get_int(srt_query* q, const char* name, int* v) {
@@ -271,6 +283,11 @@ int srt_query_get_int(srt_query* q, const char* name, int* v) {
   }
   else if (n == "rebuild.models") *v = q->rebuild && q->rebuild->models ? 1 : 0;
   else if (n == "rebuild.records") *v = q->rebuild ? (int)q->rebuild->records : 0;
+  else if (n == "sort.origin_bits") *v = srt::rayorder::OriginBits();
+  else if (n == "sort.dir_bits") *v = srt::rayorder::DirBits();
+  else if (n == "sort.bytes") *v = q->sort ? srt::stage::SaturateInt(q->sort->bytes) : 0;
+  else if (n == "sort.launches") *v = q->sort ? q->sort->launches : 0;
+  else if (n == "sort.count") *v = q->sort ? q->sort->count : 0;
   else return SRT_ERR_NOT_FOUND;
   return SRT_OK;
 }

@@ -29,6 +29,7 @@ struct QParams {
   uint32_t claim;        // rays a wave claims per atomic (a multiple of 64)
   int stack_entries;
   int refill_min;        // a wave refills when fewer lanes than this traverse (1..64)
+  const uint32_t* order; // ORDER instances only: position in the launch -> ray index, a permutation of 0 .. n-1
 };
 
 #ifndef SRT_QUERY_SUBSTEPS
@@ -156,7 +157,9 @@ __device__ __forceinline__ void write_result(const QParams& qp, const QLane& L) 
   }
 }
 
-template <bool ANY, bool HBM, bool PACK>
+// ORDER (include/srt_query_sort.h): the claimed positions [cur, end) are positions of qp.order, and a refilled lane
+// takes the ray sorted there; rays are read and results written in place through L.idx, as without it.
+template <bool ANY, bool HBM, bool PACK, bool ORDER = false>
 __global__ __launch_bounds__(256) void query_kernel(QParams qp) {
   const uint32_t lane = threadIdx.x & 63u;
   Stack<PACK> stk;
@@ -201,7 +204,12 @@ __global__ __launch_bounds__(256) void query_kernel(QParams qp) {
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(nm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nm, 0u));
         const uint32_t left = end - cur, want = (uint32_t)__popcll(nm);
         if (need && rank < left) {
-          L.idx = cur + rank;
+          if constexpr (ORDER) {
+            const uint32_t r = qp.order[cur + rank];
+            L.idx = r < qp.n ? r : qp.n - 1u;  // (a permutation by construction; the clamp keeps any word inside)
+          } else {
+            L.idx = cur + rank;
+          }
           L.dist = qp.rays[2 * (size_t)L.idx + 1].w;
           L.hit = kMiss;
           L.hit_bvh = 0u;

@@ -62,6 +62,25 @@ struct State {
 };
 
 }  // namespace rebuild
+
+namespace rayorder {
+
+// What the first sorted call adds to an object (query_sort.hip, include/srt_query_sort.h), grown only when n grows.
+struct State {
+  stage::DevPtr<uint32_t> d_pairs;   // 4 arrays of `capacity` dwords: keys_in, order_in, keys (sorted), order (sorted)
+  stage::DevPtr<uint8_t> d_temp;     // the sort's temporary storage
+  stage::DevPtr<uint32_t> d_words;   // the six bounds words (ray_order_rule.hpp)
+  uint32_t capacity = 0;
+  size_t temp_bytes = 0, bytes = 0;  // bytes: everything above
+  uint32_t last_n = 0;               // of the last sorted call
+  int launches = 0, count = 0;
+  uint32_t* keys_in() const { return d_pairs.get(); }
+  uint32_t* order_in() const { return d_pairs.get() + capacity; }
+  uint32_t* keys() const { return d_pairs.get() + 2 * (size_t)capacity; }
+  uint32_t* order() const { return d_pairs.get() + 3 * (size_t)capacity; }
+};
+
+}  // namespace rayorder
 }  // namespace srt
 
 struct srt_query : srt::stage::Stage {
@@ -75,6 +94,7 @@ struct srt_query : srt::stage::Stage {
   uint32_t n_bvhs = 0, bvh_count = 0;
   srt::query::StackPlan plan;
   int max_blocks[2] = {0, 0};  // persistent grid of the closest / any instance
+  int max_blocks_sorted[2] = {0, 0};  // of their ORDER twins
   int refill_min = 0, claim_env = 0;
   int last_blocks = 0;
   // SRT_QUERY_REFIT only (refit.hip); nothing here is allocated without the flag
@@ -89,6 +109,8 @@ struct srt_query : srt::stage::Stage {
   uint32_t first_index0 = 0;  // of BVH record 0
   int cu_count = 0;
   std::unique_ptr<srt::rebuild::State> rebuild;
+  // the first srt_query_*_sorted call only (query_sort.hip); null otherwise
+  std::unique_ptr<srt::rayorder::State> sort;
 };
 
 namespace srt {
@@ -97,6 +119,10 @@ namespace query {
 // The persistent grids of the two kernel instances q->plan selects (query.hip; at creation, and again when a
 // rebuild changes the plan).
 int PlanGrid(srt_query* q);
+
+// srt_query_closest (any: srt_query_occluded) with its argument checks, on q->stream.  `order` null: the rays in the
+// caller's order; else the device permutation of 0 .. n-1 the launch claims through (query.hip).
+int EnqueueTrace(srt_query* q, bool any, const srt_ray* rays, uint32_t n, void* out, const uint32_t* order);
 
 }  // namespace query
 

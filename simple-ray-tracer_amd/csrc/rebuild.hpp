@@ -41,6 +41,7 @@
 
 #include <cstdint>
 
+#include "ordered_word.hpp"
 #include "rebuild_rule.hpp"
 #include "refit_fold.hpp"
 
@@ -211,16 +212,8 @@ __global__ __launch_bounds__(256) void box_final_kernel(BParams bp) {
 // seg_box_kernel: one lane per triangle; the box of its owner.  Floats go through the order-preserving map to uint32, the
 //   lower bounds complemented, so every bound is an atomic max over words zeroed at launch: min and max of values are
 //   exact and commute, no neutral element and no infinity is needed, and a record's box holds its own triangles only.  A
-//   block whose triangles all have one owner folds in the block first and issues six atomics.
-__device__ __forceinline__ uint32_t ordered(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float unordered(uint32_t e) {
-  return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e);
-}
-
+//   block whose triangles all have one owner folds in the block first and issues six atomics.  (ordered / unordered:
+//   ordered_word.hpp.)
 __device__ __forceinline__ uint32_t owner_of(const BParams& bp, uint32_t t) {
   const uint32_t r = bp.owner[t];
   return r < bp.n_records ? r : bp.n_records - 1u;

@@ -28,7 +28,7 @@ from . import _lib
 from ._lib import SrtError, check, lib
 
 __all__ = [
-    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "build_lbvh", "build_lbvh_models", "UploadModelDataToGPU",
+    "Compute", "Model", "Scene", "LoadObject", "load_obj", "model_from_triangles", "refit_scene", "build_lbvh", "build_lbvh_models", "ray_order", "UploadModelDataToGPU",
     "UpdateModelMatrix", "Camera", "InputState", "progressive_frame", "PointLight", "generate_noise", "glibc_rand", "SrtError",
     "NODE_DTYPE", "BVH_DTYPE", "MAT_DTYPE", "TRI_DTYPE", "VERT_DTYPE", "LIGHT_DTYPE", "RAY_DTYPE",
     "MODEL_LIGHTS", "SPHERE_LIGHTS", "REFERENCE_OBJECTS",
@@ -427,6 +427,18 @@ def build_lbvh_models(scene: Scene, verts: np.ndarray | None = None, max_leaf: i
         bvhs[r]["count"] = starts[r + 1] - starts[r]
     tri_input = None if scene.tri_input is None else scene.tri_input[order]
     return dataclasses.replace(scene, bvhs=bvhs, nodes=nodes, tris=tris, verts=verts, tri_input=tri_input), order
+
+
+def ray_order(rays: np.ndarray, bounds: bool = False):
+    """The host mirror of the sorted ray queries' ordering rule (``srt_ray_order``, include/srt_query_sort.h) for a
+    ``RAY_DTYPE`` array: ``(order, keys)`` -- the stable sort of ``0 .. n-1`` by key and the sorted keys -- and with
+    ``bounds=True`` ``(order, keys, bounds)``, ``bounds`` the lo xyz, hi xyz of the finite origins.
+    ``Query.closest(rays, sort=True)`` traces the rays in this order.  No device is touched."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+    n = len(rays)
+    order, keys, box = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(6, np.float32)
+    check(lib().srt_ray_order(_ptr(rays), n, _ptr(order), _ptr(keys), _ptr(box)), "srt_ray_order")
+    return (order, keys, box) if bounds else (order, keys)
 
 
 # ---------------------------------------------------------------------------

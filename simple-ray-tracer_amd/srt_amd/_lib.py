@@ -381,6 +381,17 @@ _REBUILD_MODELS_SIGS = {
 }
 REBUILD_MODELS_SYMBOLS = tuple(_REBUILD_MODELS_SIGS)
 
+# include/srt_query_sort.h: coherence-sorted ray queries and the host mirror of their ordering rule (its own header and
+# version)
+_QUERY_SORT_SIGS = {
+    "srt_query_sort_abi_version": (C.c_int, []),
+    "srt_query_closest_sorted": (C.c_int, [P, P, C.c_uint32, P]),
+    "srt_query_occluded_sorted": (C.c_int, [P, P, C.c_uint32, P]),
+    "srt_ray_order": (C.c_int, [P, C.c_uint32, P, P, P]),
+    "srt_query_copy_ray_order": (C.c_int, [P, P, P, C.c_uint32]),
+}
+QUERY_SORT_SYMBOLS = tuple(_QUERY_SORT_SIGS)
+
 _lib = None
 
 
@@ -417,7 +428,8 @@ def lib() -> C.CDLL:
                                   + list(_SURFACE_SIGS.items()) + list(_REFIT_SIGS.items())
                                   + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
                                   + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())
-                                  + list(_REBUILD_LEAF_SIGS.items()) + list(_REBUILD_MODELS_SIGS.items())):
+                                  + list(_REBUILD_LEAF_SIGS.items()) + list(_REBUILD_MODELS_SIGS.items())
+                                  + list(_QUERY_SORT_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -3,7 +3,8 @@
 ``Query(scene)`` uploads a copy of the scene to the device; ``closest(rays)`` and ``occluded(rays)`` trace a
 ``torch`` tensor of rays that already lives there and return device tensors, without a host round trip or a
 synchronisation.  The results are bit-identical to the CPU oracle's ``trace_closest``.  A numpy structured
-array of ``RAY_DTYPE`` is accepted too; that path copies both ways and synchronises.
+array of ``RAY_DTYPE`` is accepted too; that path copies both ways and synchronises.  ``sort=True`` on either call
+traces the rays in a coherence-sorted order built on the device (include/srt_query_sort.h): the same results.
 """
 from __future__ import annotations
 
@@ -98,6 +99,7 @@ class Query(_Stage):
         args = (_ptr(s.bvhs), len(s.bvhs), _ptr(s.nodes), len(s.nodes), _ptr(s.tris), len(s.tris), _ptr(s.verts),
                 len(s.verts))
         self._n_tris = len(s.tris)
+        self._sorted_n = 0  # of the last sort=True call that launched
         if refit:
             self._create(*args, SRT_QUERY_REFIT, name="create_ex")
         else:
@@ -194,28 +196,45 @@ class Query(_Stage):
         self._run(lambda: fn(self.handle, C.c_void_p(rays.data_ptr()), rays.shape[0], C.c_void_p(out.data_ptr())), what)
         return out
 
-    def closest(self, rays):
+    def closest(self, rays, sort=False):
         """Closest hits of ``rays``: a :class:`Hits` over a device tensor (torch input), or a ``HIT_DTYPE``
-        array (numpy ``RAY_DTYPE`` input)."""
+        array (numpy ``RAY_DTYPE`` input).  ``sort=True`` traces the rays in a coherence-sorted order built on the
+        device (``srt_query_closest_sorted``, include/srt_query_sort.h): the same results bit for bit, faster for rays
+        that arrive incoherent and slower for rays that arrive coherent."""
         import torch
         if isinstance(rays, np.ndarray):
             dev = torch.from_numpy(np.ascontiguousarray(rays, dtype=RAY_DTYPE).view(np.float32).reshape(-1, 8))
-            hits = self.closest(dev.to(f"cuda:{self.device}"))
+            hits = self.closest(dev.to(f"cuda:{self.device}"), sort=sort)
             self.synchronize()
             return hits.numpy()
         rays_arg(rays, self.device)
         out = torch.empty((rays.shape[0], 8), dtype=torch.int32, device=rays.device)
+        if sort:
+            self._sorted_n = rays.shape[0] or self._sorted_n
+            return Hits(self._trace(lib().srt_query_closest_sorted, "srt_query_closest_sorted", rays, out))
         return Hits(self._trace(lib().srt_query_closest, "srt_query_closest", rays, out))
 
-    def occluded(self, rays):
+    def occluded(self, rays, sort=False):
         """1 where some triangle is accepted (the walk stops at the first): a uint8 ``[n]`` device tensor, or
-        a numpy array for numpy input."""
+        a numpy array for numpy input.  ``sort=True``: ``srt_query_occluded_sorted``, as :meth:`closest`."""
         import torch
         if isinstance(rays, np.ndarray):
             dev = torch.from_numpy(np.ascontiguousarray(rays, dtype=RAY_DTYPE).view(np.float32).reshape(-1, 8))
-            occ = self.occluded(dev.to(f"cuda:{self.device}"))
+            occ = self.occluded(dev.to(f"cuda:{self.device}"), sort=sort)
             self.synchronize()
             return occ.cpu().numpy()
         rays_arg(rays, self.device)
         out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+        if sort:
+            self._sorted_n = rays.shape[0] or self._sorted_n
+            return self._trace(lib().srt_query_occluded_sorted, "srt_query_occluded_sorted", rays, out)
         return self._trace(lib().srt_query_occluded, "srt_query_occluded", rays, out)
+
+    def ray_order(self):
+        """``(order, keys)`` of the last ``sort=True`` call (``srt_query_copy_ray_order``: a test and debug readback;
+        synchronises): position -> ray index, and the sorted keys.  ``SrtError`` (``SRT_ERR_STATE``) before any."""
+        n = self._sorted_n
+        order, keys = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        check(lib().srt_query_copy_ray_order(self.handle, _ptr(order), _ptr(keys), n), "srt_query_copy_ray_order")
+        return order, keys
+

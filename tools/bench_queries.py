@@ -14,6 +14,12 @@ from a profiler run of its own (no counters in it):
 
 --legacy traces every leg's rays LEGACY_REPS times through srt_trace_closest, in leg order; --legacy-trace
 reads the closest_kernel dispatches of that run (median per leg) and reports legacy_ms / closest_ms.
+
+--sorted times every leg through the sorted calls too (include/srt_query_sort.h), in the same process: per leg the
+sorted totals beside the unsorted times, and the cost of the ordering alone (bounds + keys + sort) with the traversal
+left out -- at bvh_count 0 the traversal kernel only writes every ray's miss record, so the sorted call minus the
+unsorted call there is what the ordering adds.  --legs picks legs, --rebuild-leaf N measures on a device-rebuilt tree
+(include/srt_rebuild_leaf.h).  The raw runs of DESIGN.md's "Sorted ray queries" are profiles/query_sort.json.
 Nothing here is asserted: this is a measurement tool.
 """
 from __future__ import annotations
@@ -126,6 +132,24 @@ def time_calls(torch, fn, warmup, reps):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def sorted_times(torch, lib, q, h, rp, n, hp, op, args):
+    """The sorted calls of one leg: the totals, and the ordering alone from the calls at bvh_count 0."""
+    r = {}
+    for name, fn, out in (("closest", lib.srt_query_closest_sorted, hp), ("occluded", lib.srt_query_occluded_sorted, op)):
+        med, lo, hi = time_calls(torch, lambda: fn(h, rp, n, out), args.warmup, args.reps)
+        r[f"{name}_sorted_ms"], r[f"{name}_sorted_ms_min_max"] = round(med, 4), [round(lo, 4), round(hi, 4)]
+        r[f"{name}_sorted_mrays_s"] = round(n / med / 1e3, 1)
+    q.set_bvh_count(0)  # no BVH to walk: the traversal kernel writes the miss records and nothing else
+    empty_sorted, _, _ = time_calls(torch, lambda: lib.srt_query_closest_sorted(h, rp, n, hp), args.warmup, args.reps)
+    empty_plain, _, _ = time_calls(torch, lambda: lib.srt_query_closest(h, rp, n, hp), args.warmup, args.reps)
+    q.set_bvh_count(1)
+    lib.srt_query_closest_sorted(h, rp, n, hp)  # the hits the caller checks against `occ` are a sorted call's again
+    r["sorted_empty_ms"], r["unsorted_empty_ms"] = round(empty_sorted, 4), round(empty_plain, 4)
+    r["sort_ms"] = round(empty_sorted - empty_plain, 4)
+    r.update({k: q.get_int(k) for k in ("sort.origin_bits", "sort.dir_bits", "sort.bytes", "sort.launches")})
+    return r
+
+
 def run_new(legs, args):
     import torch
     from srt_amd import _lib
@@ -134,12 +158,15 @@ def run_new(legs, args):
 
     legacy = legacy_times(args.legacy_trace) if args.legacy_trace else {}
     results = []
-    for leg in LEGS:
+    for leg in [l for l in LEGS if not args.legs or "/".join(l) in args.legs.split(",")]:
         scene, rays = legs[leg]
         n = len(rays)
         stream = torch.cuda.current_stream()
-        with Query(scene, stream=stream.cuda_stream or None) as q:
+        kw = dict(refit=True, rebuild=True, rebuild_leaf=args.rebuild_leaf) if args.rebuild_leaf else {}
+        with Query(scene, stream=stream.cuda_stream or None, **kw) as q:
             q.set_bvh_count(1)
+            if args.rebuild_leaf:
+                q.rebuild(torch.from_numpy(scene.verts.view(np.float32).reshape(-1, 8).copy()).cuda())
             dev = torch.from_numpy(rays.view(np.float32).reshape(-1, 8).copy()).cuda()
             hits = torch.empty((n, 8), dtype=torch.int32, device="cuda")
             occ = torch.empty((n,), dtype=torch.uint8, device="cuda")
@@ -153,6 +180,7 @@ def run_new(legs, args):
             with ctx:
                 c_med, c_min, c_max = time_calls(torch, lambda: lib.srt_query_closest(h, rp, n, hp), args.warmup, args.reps)
                 o_med, o_min, o_max = time_calls(torch, lambda: lib.srt_query_occluded(h, rp, n, op), args.warmup, args.reps)
+                extra = sorted_times(torch, lib, q, h, rp, n, hp, op, args) if args.sorted else {}
             torch.cuda.synchronize()
             hit_fraction = float((hits[:, 0] != -1).float().mean())
             assert bool(((hits[:, 0] != -1) == (occ != 0)).all())
@@ -163,6 +191,11 @@ def run_new(legs, args):
                  "occluded_mrays_s": round(n / o_med / 1e3, 1),
                  "blocks": q.get_int("launch.blocks"), "refill_min": q.get_int("refill.min"),
                  "stack_entries": q.get_int("stack.entries"), "warmup": args.warmup, "reps": args.reps}
+            if args.rebuild_leaf:
+                r["rebuild_leaf"] = args.rebuild_leaf
+            if extra:
+                r.update(extra)
+                r["sorted_over_unsorted"] = round(r["closest_sorted_ms"] / c_med, 3)
             if leg in legacy:
                 r["legacy_closest_kernel_ms"] = round(legacy[leg], 4)
                 r["legacy_over_closest"] = round(legacy[leg] / c_med, 3)
@@ -185,6 +218,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--legacy", action="store_true", help="run the rays through srt_trace_closest (for the profiler)")
     ap.add_argument("--legacy-trace", help="output directory of the profiler run of --legacy")
+    ap.add_argument("--sorted", action="store_true", help="also time every leg through the sorted calls (srt_query_sort.h)")
+    ap.add_argument("--legs", help="comma-separated legs to run (rubik/camera, rubik/surface, knot/camera, knot/surface)")
+    ap.add_argument("--rebuild-leaf", type=int, default=0, help="measure on a device-rebuilt tree with this max_leaf")
     ap.add_argument("--out", help="write the legs to this JSON file")
     args = ap.parse_args()
     if args.warmup < 3 or args.reps < 10:
