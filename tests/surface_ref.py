@@ -53,15 +53,16 @@ def as_rgb(texels):
     return out
 
 
-def sample(texels, s, t):
-    """texture(sampler2D, vec2(s, t)).xyz at level 0, GL_LINEAR, GL_REPEAT on arrays of coordinates: non-finite
-    coordinates read as 0, texels are c / 255, the weighted texels are summed ((00 + 10) + 01) + 11."""
+def sample_terms(texels, s, t):
+    """`sample` with its intermediate values: {"nonfinite" (per axis), "frac", "x", "a", "i0", "i1" (each an (s, t)
+    pair of arrays), "weights" (w00, w10, w01, w11), "out"}."""
     tex = as_rgb(texels)
     h, w = tex.shape[:2]
     s, t = np.asarray(s, np.float32).copy(), np.asarray(t, np.float32).copy()
     with np.errstate(all="ignore"):
-        s[~(np.abs(s) <= FLT_MAX)] = 0
-        t[~(np.abs(t) <= FLT_MAX)] = 0
+        bad_s, bad_t = ~(np.abs(s) <= FLT_MAX), ~(np.abs(t) <= FLT_MAX)
+        s[bad_s] = 0
+        t[bad_t] = 0
         s = s - np.floor(s)
         t = t - np.floor(t)
         x, y = s * F(w) - F(0.5), t * F(h) - F(0.5)
@@ -79,13 +80,21 @@ def sample(texels, s, t):
         out = ((w00[..., None] * tx[j0, i0] + w10[..., None] * tx[j0, i1]) + w01[..., None] * tx[j1, i0]) \
             + w11[..., None] * tx[j1, i1]
     assert out.dtype == np.float32
-    return out
+    return {"nonfinite": (bad_s, bad_t), "frac": (s, t), "x": (x, y), "a": (a, b), "i0": (i0, j0), "i1": (i1, j1),
+            "weights": (w00, w10, w01, w11), "out": out}
 
 
-def shade(scene, rays, hits, *, textures=None, tex_albedo=None, bvh_count=None, frames=None):
+def sample(texels, s, t):
+    """texture(sampler2D, vec2(s, t)).xyz at level 0, GL_LINEAR, GL_REPEAT on arrays of coordinates: non-finite
+    coordinates read as 0, texels are c / 255, the weighted texels are summed ((00 + 10) + 01) + 11."""
+    return sample_terms(texels, s, t)["out"]
+
+
+def shade(scene, rays, hits, *, textures=None, tex_albedo=None, bvh_count=None, frames=None, terms=None):
     """srt_surface_shade: ATTR_DTYPE records of RAY_DTYPE `rays` and HIT_DTYPE `hits` over `scene`'s arrays.
     `textures`: the uploaded set (list of (H, W, C) uint8); `tex_albedo`: (n_mats, 3) or None, srt_surface_create's
-    argument; `frames`: (n_bvhs, 16) to override the scene's (update_model_matrix)."""
+    argument; `frames`: (n_bvhs, 16) to override the scene's (update_model_matrix); `terms`: a dict that receives the
+    intermediate values of the hit records ("idx", their positions, and "mp", "denom", "v", "w", "u")."""
     n = len(rays)
     out = np.zeros(n, ATTR_DTYPE)
     textures = textures or []
@@ -115,6 +124,8 @@ def shade(scene, rays, hits, *, textures=None, tex_albedo=None, bvh_count=None, 
         u = F(1) - v - w
         uv0, uv1, uv2 = (scene.verts["uv"][tv[:, k]] for k in range(3))
         uv = (u[:, None] * uv0 + v[:, None] * uv1) + w[:, None] * uv2
+    if terms is not None:
+        terms.update(idx=idx, mp=mp, denom=denom, v=v, w=w, u=u)
     mat = scene.mats[scene.tris["mat"][tri]]
     alb = mat["diffuse"].astype(np.float32).copy()
     sampled = mat["use_texture"] != 0
