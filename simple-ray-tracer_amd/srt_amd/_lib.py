@@ -392,6 +392,25 @@ _QUERY_SORT_SIGS = {
 }
 QUERY_SORT_SYMBOLS = tuple(_QUERY_SORT_SIGS)
 
+
+class UpsampleParams(C.Structure):
+    """srt_upsample_params (include/srt_upsample.h)."""
+    _fields_ = [("normal_squarings", C.c_uint32), ("sigma_depth", C.c_float)]
+
+
+# include/srt_upsample.h: guided upsampling of low-resolution frames (its own header and version)
+_UPSAMPLE_SIGS = {
+    "srt_upsample_abi_version": (C.c_int, []),
+    "srt_upsample_create": (C.c_int, [C.c_int, P, C.c_int, C.c_int, C.c_int, C.POINTER(P)]),
+    "srt_upsample_destroy": (C.c_int, [P]),
+    "srt_upsample_stream": (P, [P]),
+    "srt_upsample_get_int": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_int)]),
+    "srt_upsample_get_params": (C.c_int, [P, C.POINTER(UpsampleParams)]),
+    "srt_upsample_set_params": (C.c_int, [P, C.POINTER(UpsampleParams)]),
+    "srt_upsample_run": (C.c_int, [P, P, C.c_int, P, P, P, P]),
+}
+UPSAMPLE_SYMBOLS = tuple(_UPSAMPLE_SIGS)
+
 _lib = None
 
 
@@ -429,7 +448,7 @@ def lib() -> C.CDLL:
                                   + list(_TEMPORAL_DEFORM_SIGS.items()) + list(_SURFACE_REFIT_SIGS.items())
                                   + list(_SCENE_REFIT_SIGS.items()) + list(_REBUILD_SIGS.items())
                                   + list(_REBUILD_LEAF_SIGS.items()) + list(_REBUILD_MODELS_SIGS.items())
-                                  + list(_QUERY_SORT_SIGS.items())):
+                                  + list(_QUERY_SORT_SIGS.items()) + list(_UPSAMPLE_SIGS.items())):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args
